@@ -1,8 +1,13 @@
 """Benchmark: Mrays/s of the MI355X path tracer on BASELINE.json's headline configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and no more: scene set-up, W warm-up frames, the K timed frames, the outputs of
+the last timed frame written under DIR when --dump-outputs is given (dump_outputs()), and the JSON line.  Every other
+leg described below -- single_frame, the other RNG contract (streams_of_32 / contract_one_stream) and cpu_baseline --
+runs only with --full, after the timed frames, and leaves the headline figures as they are.
 
 One step = one frame of the config (1920x1080x256 spp bunny scene with full materials by default),
 tile-sharded across the N ranks (the balanced tile plan, RP_SHARD_BALANCED: tiles dealt by a learned cost; strong
@@ -247,12 +252,54 @@ class FrameSeq:
         return f0, frame_seed(seed, nbatch, width, height, f0)
 
 
+# --dump-outputs: elements kept of each array (float32 BGRA bytes: 32 MiB; float64 linear RGB: 24 MiB; 64 MB in all)
+DUMP_BGRA_ELEMS = 1 << 23
+DUMP_RGB_ELEMS = 3 << 20
+DUMP_SEED = 0x0D15EA5E
+
+
+def dump_sample(n: int, cap: int):
+    """Rows kept of an n-row output of which at most cap fit: all of them (None), or a fixed, seeded, sorted sample."""
+    import numpy as np
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(dirname: str, frame_bgra, shard_rgb, counters) -> dict:
+    """What the timed path handed its caller for the last timed frame, as DIR/<name>.npy: frame_bgra (float32, pixels x 4:
+    the assembled to_srgb_u8 frame in B, G, R, A order, a byte per element), shard_rgb (float64, slots x 3: this rank's
+    linear RGB in slot order, the render kernel's own output) and counters (float64: the last launch's counters, summed
+    over the ranks).  A frame too large for the budget is sampled by dump_sample (the same rows every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for name, t, width, cap, dtype in (("frame_bgra", frame_bgra, 4, DUMP_BGRA_ELEMS // 4, np.float32),
+                                       ("shard_rgb", shard_rgb, 3, DUMP_RGB_ELEMS // 3, np.float64)):
+        a = t.reshape(-1, width)
+        rows = dump_sample(a.shape[0], cap)
+        if rows is not None:
+            import torch
+            a = a[torch.from_numpy(rows).to(a.device)]
+        arrays[name] = a.cpu().numpy().astype(dtype)
+    arrays["counters"] = counters.cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)  # one launch of 16 frames
     ap.add_argument("--warmup", type=int, default=8)  # spread over the in-flight workspaces: each learns its tile costs
     ap.add_argument("--config", default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed frames also run the legs reported beside the headline: single_frame, the other "
+                         "RNG contract (--contract-steps) and, on one GPU, cpu_baseline; without it none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's outputs as DIR/<name>.npy (dump_outputs: frame_bgra, shard_rgb, "
+                         "counters; rank 0)")
     ap.add_argument("--spp", type=int, default=0, help="override the config's spp (0 = config)")
     ap.add_argument("--samples-per-stream", type=int, default=0,
                     help="rp_render_params.samples_per_stream, the RNG contract (0 = auto: SURVEY.md 8c's one stream "
@@ -262,7 +309,7 @@ def main():
                     help="tile side in pixels (rp_render_params.tile_w/tile_h; 0 = the config's 32): scheduling only, "
                          "the image does not depend on it")
     ap.add_argument("--cpu-spp", type=int, default=0, help="override the CPU baseline runs' spp (0 = per run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--inflight", type=int, default=0,
                     help="frames in flight: consecutive frames alternate over this many streams and workspaces "
                          "(0 = 1 on one GPU, 3 on several)")
@@ -273,7 +320,7 @@ def main():
                     help="RP_FRAME_ORDER_* of a launch of several frames (pixel: interleaved with a pixel's frames "
                          "consecutive, C3 -0.66 %% against interleaved, profiles/r6/c3_v58_knob_sweep_ab.json)")
     ap.add_argument("--no-single-frame", action="store_true",
-                    help="skip the single-frame-per-launch timing reported beside a frame-sequence headline")
+                    help="with --full: skip the single-frame-per-launch timing reported beside a frame-sequence headline")
     ap.add_argument("--shard-of", type=int, default=0,
                     help="diagnostic, one GPU: render only shard --shard of this many (the per-rank work of an N-GPU "
                          "run), no gather; not a bench line")
@@ -281,8 +328,8 @@ def main():
     ap.add_argument("--shard-map", default="auto", choices=("auto", "interleave", "balanced"),
                     help="tile deal across ranks (rp_render_params.shard_map); auto = balanced for N > 1 or --shard-of")
     ap.add_argument("--contract-steps", type=int, default=-1,
-                    help="frames timed after the headline under the other RNG contract: 32-sample streams when the "
-                         "headline is SURVEY.md 8c's one stream per pixel (N = 1), reported as streams_of_32, else the "
+                    help="with --full: frames timed after the headline under the other RNG contract: 32-sample streams "
+                         "when the headline is SURVEY.md 8c's one stream per pixel (N = 1), reported as streams_of_32, else the "
                          "one-stream contract, reported as contract_one_stream (-1 = a launch's worth for the default "
                          "workload, 0 = off)")
     ap.add_argument("--opt", action="append", default=[],
@@ -467,6 +514,12 @@ def main():
     if dump and rank == 0 and not args.shard_of:  # tests only: the timed run's last launch, assembled BGRA8 frames
         import numpy as np
         np.save(dump, frames[:sizes[-1] * params.width * params.height * 4].cpu().numpy())
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed step: frame sizes[-1] - 1 of the last launch
+        last, f, npx = (state["k"] - 1) % F_, sizes[-1] - 1, params.width * params.height
+        dumped = dump_outputs(args.dump_outputs, frames[f * npx * 4:(f + 1) * npx * 4],
+                              bufs[last][f * n3:f * n3 + 3 * nslots], ctrs[last])
+        log(f"[rank 0] outputs of timed frame {args.steps - 1} written to {args.dump_outputs}: {dumped}")
     kernel_s = sum(kdur) / args.steps  # per frame: launch durations over the frames they rendered
     kernel_launch_ms = sum(kdur) / len(kdur) * 1e3
     if F_ > 1:
@@ -477,7 +530,7 @@ def main():
 
     # single-frame latency beside the frame-sequence throughput: one frame per launch, sequential, same workspaces
     single = None
-    if L > 1 and not args.no_single_frame:
+    if args.full and L > 1 and not args.no_single_frame:
         nsf = 3
         for _ in range(F_):  # one lone frame per workspace first: it learns the unit durations a lone frame schedules
             step(1)          # by (rp_scene_options.unit_order AUTO: one stream per pixel)
@@ -512,7 +565,7 @@ def main():
     csteps = args.contract_steps if args.contract_steps >= 0 else (
         (Lc if Lc > 1 else 3) if (sps_auto or not args.samples_per_stream) and not (args.shard_of or args.spp or args.tile)
         else 0)
-    if csteps > 0 and params.spp > F.RP_SAMPLES_PER_STREAM:
+    if args.full and csteps > 0 and params.spp > F.RP_SAMPLES_PER_STREAM:
         side_key = "streams_of_32" if one_stream else "contract_one_stream"
         spc = shard_params(replace(params, samples_per_stream=side_sps), rank, world)
         for w in wss:
@@ -618,7 +671,8 @@ def main():
         out = {
             "metric": METRIC, "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "full": args.full,
+            **({"dump_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped else {}),
             "note": "frame-sequence throughput: the K timed frames in launches of frames_per_launch (no frame is "
                     "available before its launch ends); single_frame = one frame per launch (lone-frame latency)",
             "data": "reference assets (bunny.obj, earthmap.tga packed in-repo) + synthesized sky panorama",
@@ -647,7 +701,7 @@ def main():
             "single_frame": single,
             **({side_key: side} if side_key else {}),
         }
-        if world == 1 and not args.no_cpu_baseline and not args.shard_of:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.shard_of:
             log("[rank 0] cpu baseline ...")
             cb = cpu_baseline(args.config, CPU_RUNS, args.cpu_spp)
             out["cpu_baseline"] = cb

@@ -10,9 +10,6 @@ for p in (REPO, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-REFERENCE = "/root/reference"
-HAVE_REFERENCE = os.path.isdir(os.path.join(REFERENCE, "src"))
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (runs through librp.so on the device)")

@@ -299,3 +299,34 @@ def test_bench_frame_sequence_seeds():
         allf = sorted(phases[0] | phases[1] | phases[2])
         assert all(y - x >= nb * W * H for x, y in zip(allf, allf[1:]))
     assert b.frame_seed(b.U64, 1, 1, 1, 1) == 0  # u64 wrap, like rp_render_params.seed
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """bench.py --dump-outputs: an output that fits its budget is written whole, a larger one as the same sorted rows
+    every run (dump_sample is seeded), in float32 (the frame's bytes, exact) and float64, and the budgets of a dump
+    stay under 64 MB together."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.dump_sample(100, 100) is None and b.dump_sample(0, 8) is None
+    rows = b.dump_sample(1000, 64)
+    assert rows.shape == (64,) and np.array_equal(rows, b.dump_sample(1000, 64))
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 1000
+    assert 4 * b.DUMP_BGRA_ELEMS + 8 * b.DUMP_RGB_ELEMS + 8 * 64 + 3 * 128 <= 64_000_000
+    assert b.DUMP_BGRA_ELEMS >= 1920 * 1080 * 4  # the headline's frame is written whole
+    frame = torch.arange(5 * 7 * 4, dtype=torch.int64).remainder(256).to(torch.uint8)
+    rgb = torch.linspace(0.0, 1.0, 3 * 40, dtype=torch.float64)
+    ctr = torch.tensor([11, 5, 0, 0], dtype=torch.int64)
+    shapes = b.dump_outputs(str(tmp_path / "o"), frame, rgb, ctr)
+    assert shapes == {"frame_bgra": [35, 4], "shard_rgb": [40, 3], "counters": [4]}
+    got = {n: np.load(tmp_path / "o" / (n + ".npy")) for n in shapes}
+    assert got["frame_bgra"].dtype == np.float32 and np.array_equal(got["frame_bgra"].reshape(-1), frame.numpy())
+    assert got["shard_rgb"].dtype == np.float64 and np.array_equal(got["shard_rgb"].reshape(-1), rgb.numpy())
+    assert got["counters"].dtype == np.float64 and got["counters"].tolist() == [11.0, 5.0, 0.0, 0.0]
+    b.DUMP_RGB_ELEMS = 3 * 16  # a shard past its budget: 16 of the 40 rows, the sampled ones
+    b.dump_outputs(str(tmp_path / "o"), frame, rgb, ctr)
+    small = np.load(tmp_path / "o" / "shard_rgb.npy")
+    assert np.array_equal(small, rgb.numpy().reshape(40, 3)[b.dump_sample(40, 16)])

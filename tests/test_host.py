@@ -1,22 +1,31 @@
 """Host-side pieces (librp_host.so) against the oracle's restatements and the reference's own assets:
 obj::load (mesh.rs:145-183), tga::load/save (image.rs:73-137), to_srgb_u8 (utility.rs:212-220),
 Transformation::lookat (utility.rs:172-177), and the packed asset fixtures used on the GPU box.
+
+The reference's asset files are stored gzip-compressed under tests/golden/ (bunny.obj.gz, bunny_flat.obj.gz,
+earthmap.tga.gz): the packed fixtures the package renders from are re-derived from them here.
 """
+import gzip
 import os
 
 import numpy as np
 import pytest
 
-from conftest import HAVE_REFERENCE, REFERENCE
-
-ref_only = pytest.mark.skipif(not HAVE_REFERENCE, reason="reference assets not mounted")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@ref_only
+def _stored_asset(tmp_path, name):
+    """tests/golden/<name>.gz unpacked into tmp_path: the reference's asset file, byte for byte."""
+    out = tmp_path / name
+    with gzip.open(os.path.join(GOLDEN, name + ".gz"), "rb") as f:
+        out.write_bytes(f.read())
+    return str(out)
+
+
 @pytest.mark.parametrize("name", ["bunny", "bunny_flat"])
-def test_obj_load_matches_oracle_and_fixture(oracle, name):
+def test_obj_load_matches_oracle_and_fixture(oracle, name, tmp_path):
     from rtpotato import assets
-    path = os.path.join(REFERENCE, "assets", name + ".obj")
+    path = _stored_asset(tmp_path, name + ".obj")
     m = assets.obj_load(path)
     p, n, uv, idx = oracle.obj_load(path)
     assert np.array_equal(m.positions, p) and np.array_equal(m.normals, n)
@@ -26,7 +35,6 @@ def test_obj_load_matches_oracle_and_fixture(oracle, name):
     assert np.array_equal(fx["normals"], m.normals) and np.array_equal(fx["uvs"], m.uvs)
 
 
-@ref_only
 def test_obj_bunny_shape():
     """SURVEY.md 2 row 14: bunny.obj has 2,503 v, 2,503 vn, 0 vt, 4,968 tris of `f a//a` -> 2,503 unique
     (p, n, t) vertices; bunny_flat.obj dedups to 14,902 vertices."""
@@ -81,10 +89,9 @@ def test_tga_roundtrip_and_flip(tmp_path, oracle):
     assert got[1, 0].tolist() == [3, 2, 1, 255] and got[0, 0].tolist() == [12, 11, 10, 255]
 
 
-@ref_only
-def test_earthmap_fixture():
+def test_earthmap_fixture(tmp_path):
     from rtpotato import assets
-    img = assets.tga_load(os.path.join(REFERENCE, "assets", "earthmap.tga"))
+    img = assets.tga_load(_stored_asset(tmp_path, "earthmap.tga"))
     assert img.shape == (512, 1024, 4)
     assert np.array_equal(img, assets.load_image("earthmap"))
 

@@ -5,14 +5,15 @@
 #
 # STEPS, run in order, each under its own time limit; the first failure (a crash, abort or time limit) ends the session:
 #   tests              pytest -m gpu (TESTS_K: a -k expression, may hold spaces; PYTEST_ARGS: more words)
-#   bench_<CFG>        bench.py --config CFG (BENCH_ARGS appended; the CPU baseline only for C3 unless NO_CPU=1)
+#   bench_<CFG>        bench.py --full --config CFG (BENCH_ARGS appended; the CPU baseline only for C3 unless NO_CPU=1)
 #   shards_<CFG>[.<L>] tools/shard_scaling.py: every shard of SHARD_NS (default 1,8) on one GPU, SHARD_REPS reps,
 #                      SHARD_ARGS (or SHARD_ARGS_<L> for a labelled run), library SHARD_LIB_<L> (default main)
 #   shardtrace_<CFG>   rocprofv3 --kernel-trace around one tools/shard_scaling.py run (SHARD_NS, SHARD_ARGS)
 #   diag_<CFG>         tools/diag.py with the diagnostic build (phase shares, node visits, lane utilisation)
 #   trace_<CFG>        rocprofv3 --kernel-trace --stats around bench.py (the kernel's average launch duration: every launch
 #                      of the run renders the bench's frames per launch, no lone-frame or contract launches)
-#   tracedrv_<CFG>     rocprofv3 --kernel-trace --stats around the driver's command (--steps 20 --warmup 5)
+#   tracedrv_<CFG>     rocprofv3 --kernel-trace --stats around the driver's command with its side legs (--steps 20
+#                      --warmup 5 --full)
 #   pmc_<CFG>          six rocprofv3 --pmc passes over one bench launch -> tools/roofline.py record (+ the diag record
 #                      PMC_DIAG, default gpurun_out/${TAG}_<CFG>_diag.json, if present; PMC_LABEL names a labelled run)
 #   units_<CFG>        tools/unit_times.py: the longest measured unit per tile of a whole frame (UNITS_ARGS)
@@ -30,6 +31,7 @@ TAG=${TAG:-s}
 CFG=${CFG:-C3}
 P=gpurun_out/${TAG}_progress.txt
 M=gpurun_out/${TAG}_manifest.txt
+O=${P%/*}  # the output folder
 echo "start $(date +%T)" > $P
 : > $M
 step() { echo "$1 $(date +%T)" >> $P; }
@@ -41,11 +43,11 @@ pmc() {  # lib cfg name counters...   (PMC_BENCH_ARGS: the bench frames, default
   local lib=$1 cfg=$2 name=$3; shift 3
   local out=gpurun_out/${TAG}_${cfg}${PMC_LABEL:+_$PMC_LABEL}_pmc_$name cmd
   local ba=${PMC_BENCH_ARGS:-$(pmcframes $cfg)}
-  cmd="rocprofv3 --pmc $* -- python3 bench.py --config $cfg $ba --no-cpu-baseline --contract-steps 0"
+  cmd="rocprofv3 --pmc $* -- python3 bench.py --full --config $cfg $ba --no-cpu-baseline --contract-steps 0"
   step "pmc $cfg $name"
   made "$out" "RP_LIB=$lib $cmd"
   RP_LIB=$lib timeout -s KILL 300 rocprofv3 --pmc "$@" -d $out -o run --output-format csv -- \
-    python3 bench.py --config $cfg $ba --no-cpu-baseline --contract-steps 0 > $out.json 2> $out.err
+    python3 bench.py --full --config $cfg $ba --no-cpu-baseline --contract-steps 0 > $out.json 2> $out.err
 }
 LIB=raytracing-potato_amd/lib/librp.so
 libpath() { [ "$1" = main ] && echo $LIB || echo raytracing-potato_amd/lib/librp_$1.so; }
@@ -58,7 +60,7 @@ for s in ${STEPS:-tests}; do
         -p no:cacheprovider ${TESTS_K:+-k "$TESTS_K"} ${PYTEST_ARGS:-} > gpurun_out/${TAG}_tests.log 2>&1 || { step "tests failed"; exit 1; } ;;
     bench_*)
       cfg=${s#bench_}; read st wu <<< "$(frames $cfg)"
-      cpu=""; { [ $cfg != C3 ] || [ -n "${NO_CPU:-}" ]; } && cpu=--no-cpu-baseline
+      cpu="--full"; { [ $cfg != C3 ] || [ -n "${NO_CPU:-}" ]; } && cpu="--full --no-cpu-baseline"  # the side legs run with --full
       step "bench $cfg"
       made gpurun_out/${TAG}_${cfg}_bench.json "python3 bench.py --config $cfg --steps $st --warmup $wu $cpu ${BENCH_ARGS:-}"
       timeout -k 10 600 python3 bench.py --config $cfg --steps $st --warmup $wu $cpu ${BENCH_ARGS:-} \
@@ -96,9 +98,9 @@ for s in ${STEPS:-tests}; do
       # average with the line's roofline.kernel_ms_all_launches (every launch of the process, side runs included)
       cfg=${s#tracedrv_}
       step "tracedrv $cfg"
-      made gpurun_out/${TAG}_${cfg}_tracedrv "rocprofv3 --kernel-trace --stats -- python3 bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline"
+      made $O/${TAG}_${cfg}_tracedrv "rocprofv3 --kernel-trace --stats -- python3 bench.py --config $cfg --steps 20 --warmup 5 --full --no-cpu-baseline"
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_${cfg}_tracedrv -o run --output-format csv -- \
-        python3 bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline \
+        python3 bench.py --config $cfg --steps 20 --warmup 5 --full --no-cpu-baseline \
         > gpurun_out/${TAG}_${cfg}_bench_drv_under_rocprof.json 2> gpurun_out/${TAG}_${cfg}_tracedrv.err || exit 1 ;;
     pmc_*)
       cfg=${s#pmc_}
