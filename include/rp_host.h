@@ -78,6 +78,26 @@ int rph_stdrng_u64(const uint8_t seed[32], uint64_t first, uint64_t n, uint64_t*
  * floor(n / d) == (n * m) >> s (64-bit product) for every n < 2^31.  RP_EINVAL for d == 0. */
 int rph_make_div32(uint32_t d, uint32_t* m, uint32_t* s);
 
+/* Test hook: what a render decides before its first launch (raytracing-potato_amd/csrc/rp_schedule.h rps::plan_launch,
+ * the same header librp.so's render_shard calls), for n_frames frames of an rp_render_params given field by field, the
+ * scheduling fields of the scene's resolved options and the render lanes the scene keeps resident.  The tiling's
+ * outputs (n_shard_tiles .. block_words) are filled whenever the params are valid.  Returns the render's own refusal
+ * (RP_EINVAL, message: rph_last_error) or RP_OK. */
+typedef struct rph_launch_plan {
+  uint32_t n_shard_tiles, nbatch;
+  uint32_t plan_block;     /* rps::plan_block(frame tiles, num_shards) */
+  uint64_t n_slots;
+  uint64_t gather_stride;  /* rps::stage_slots: rp_gather_stride */
+  uint64_t block_words;    /* rps::pack_words(t, true, n_frames): rp_frames_block_words */
+  uint32_t queue_groups, queue_chunk, frames_inter, sortable, measure;
+  uint32_t grid;           /* blocks of the launch (rps::grid_for) */
+  uint64_t n_queue, out_stride;
+  uint32_t dv_units[2], dv_tiles_x[2], dv_chunk[2]; /* the launch's make_div32 constants, {m, s} */
+} rph_launch_plan;
+int rph_plan_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w, uint32_t tile_h,
+                    uint32_t shard, uint32_t num_shards, uint32_t samples_per_stream, uint32_t shard_map, uint32_t n_frames,
+                    uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes, rph_launch_plan* out);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

@@ -14,6 +14,7 @@
 
 #include "rp_bvh.h"
 #include "rp_kernel.h"
+#include "rp_schedule.h"
 
 namespace {
 
@@ -737,6 +738,59 @@ int rph_make_div32(uint32_t d, uint32_t* m, uint32_t* s) {
   *m = v.m;
   *s = v.s;
   return RP_OK;
+}
+
+int rph_plan_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w, uint32_t tile_h,
+                    uint32_t shard, uint32_t num_shards, uint32_t samples_per_stream, uint32_t shard_map, uint32_t n_frames,
+                    uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes, rph_launch_plan* out) {
+  if (!out) return fail("rph_plan_launch: out is NULL");
+  *out = rph_launch_plan{};
+  rp_render_params p{};
+  p.width = width;
+  p.height = height;
+  p.spp = spp;
+  p.max_bounce = max_bounce;
+  p.tile_w = tile_w;
+  p.tile_h = tile_h;
+  p.shard = shard;
+  p.num_shards = num_shards;
+  p.samples_per_stream = samples_per_stream;
+  p.shard_map = shard_map;
+  rp_scene_options opt{};
+  opt.unit_queues = unit_queues;
+  opt.queue_chunk = queue_chunk;
+  rps::LaunchPlan lp{};
+  if (!rps::make_tiling(&p, lp.t).code) {
+    out->n_shard_tiles = lp.t.n_shard_tiles;
+    out->nbatch = lp.t.nbatch;
+    out->plan_block = rps::plan_block(lp.t.n_tiles, lp.t.shards);
+    out->n_slots = lp.t.n_slots;
+    out->gather_stride = rps::stage_slots(lp.t);
+    out->block_words = rps::pack_words(lp.t, true, n_frames);
+  }
+  auto refuse = [](const rps::Refusal& r) {
+    g_err = r.msg;
+    return r.code;
+  };
+  rps::Refusal r = rps::plan_launch(&p, n_frames, frame_order, opt, lp);
+  if (r.code) return refuse(r);  // nothing planned
+  r = rps::launch_limits(lp, lanes);
+  const rpk::KParams& kp = lp.kp;
+  out->queue_groups = kp.queue_groups;
+  out->queue_chunk = kp.queue_chunk;
+  out->frames_inter = kp.frames_inter;
+  out->sortable = lp.sortable;
+  out->measure = lp.measure;
+  out->grid = (uint32_t)rps::grid_for(kp.n_queue, lanes / rpk::RENDER_BLOCK);
+  out->n_queue = kp.n_queue;
+  out->out_stride = kp.out_stride;
+  const rpk::Div32 dv[3] = {kp.dv_units, kp.dv_tiles_x, kp.dv_chunk};
+  uint32_t* const dst[3] = {out->dv_units, out->dv_tiles_x, out->dv_chunk};
+  for (int i = 0; i < 3; i++) {
+    dst[i][0] = dv[i].m;
+    dst[i][1] = dv[i].s;
+  }
+  return r.code ? refuse(r) : RP_OK;
 }
 
 }  // extern "C"

@@ -137,9 +137,17 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_workspace_tile_costs", "rp_workspace_set_tile_costs", "rp_scene_build_times",
               "rp_workspace_frame_info", "rp_workspace_reserve_frames", "rp_render_frames_device_ws", "rp_frames_gather",
               "rp_workspace_unit_order", "rp_frames_block_words", "rp_frames_pack", "rp_frames_unpack"]
+class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
+    _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
+                ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
+                ("queue_chunk", c_uint32), ("frames_inter", c_uint32), ("sortable", c_uint32), ("measure", c_uint32),
+                ("grid", c_uint32), ("n_queue", c_uint64), ("out_stride", c_uint64), ("dv_units", c_uint32 * 2),
+                ("dv_tiles_x", c_uint32 * 2), ("dv_chunk", c_uint32 * 2)]
+
+
 HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save", "rph_free", "rph_to_srgb_u8",
                 "rph_lookat", "rph_sky_panorama", "rph_bvh_selfcheck", "rph_bvh_traversal_stats", "rph_bvh_selfcheck_ex", "rph_bvh_traversal_stats_ex", "rph_bvh_tree_hash", "rph_last_error",
-                "rph_stdrng_u64", "rph_make_div32"]
+                "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch"]
 
 
 def rp_lib_path() -> str:
@@ -261,6 +269,7 @@ def host() -> ctypes.CDLL:
     lib.rph_last_error.restype = c_char_p
     lib.rph_stdrng_u64.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p]
     lib.rph_make_div32.argtypes = [c_uint32, POINTER(c_uint32), POINTER(c_uint32)]
+    lib.rph_plan_launch.argtypes = [c_uint32] * 14 + [c_uint64, POINTER(rph_launch_plan)]
     _host = lib
     return lib
 

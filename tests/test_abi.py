@@ -252,7 +252,7 @@ def test_bench_launch_sizes():
 
 
 def test_bench_frames_per_launch_cap():
-    """bench.py keeps a launch's units below 2^31 (rp_api.cpp refuses more): C3 takes its 16 frames, C5 15, C4 (1,024 spp,
+    """bench.py keeps a launch's units below 2^31 (rp_schedule.h plan_launch refuses more): C3 takes its 16 frames, C5 15, C4 (1,024 spp,
     32 batches) 16 of its 32 allowed."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))

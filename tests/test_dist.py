@@ -130,6 +130,7 @@ def test_block_deal_keeps_counts_and_compact_squares():
     totals stay balanced.  block = 1 is the per-tile deal."""
     from rtpotato.dist import deal_tiles, shard_params
     from rtpotato.scene import RenderParams, shard_slot_count
+    from test_schedule import plan_block
     rng = np.random.default_rng(7)
     for (W, H, tx, ty) in ((4096, 4096, 128, 128), (1920, 1080, 60, 34)):
         p = RenderParams(W, H, 1, 8, 0)
@@ -139,8 +140,10 @@ def test_block_deal_keeps_counts_and_compact_squares():
         cost = ((100 + 900 * (r2 < 0.5)) * rng.uniform(0.8, 1.2, (ty, tx))).astype(np.int64).reshape(-1)
         assert np.array_equal(deal_tiles(cost, 8, tx, 1), deal_tiles(cost, 8))
         for world in (2, 3, 8):
-            # rp_api.cpp plan_block: 4 x 4 or 2 x 2 blocks while every rank gets >= 32 of them
-            block = next((b for b in (4, 2) if n >= 32 * world * b * b), 1)
+            # rp_schedule.h plan_block (through the host library's hook): 4 x 4 or 2 x 2 blocks while every rank gets
+            # >= 32 of them
+            block = plan_block(p, world)
+            assert block == next((b for b in (4, 2) if n >= 32 * world * b * b), 1)
             order = deal_tiles(cost, world, tx, block)
             assert np.array_equal(np.sort(order), np.arange(n))
             loads = np.zeros(world)
@@ -211,7 +214,7 @@ def test_balanced_gather_rebuilds_frame(tmp_path, world):
 
 def test_block_deal_ragged_grid():
     """on a grid whose tile counts are not multiples of the block, the edge blocks hold fewer than block^2
-    tiles and the deal's units of block^2 consecutive sorted positions then straddle two blocks (rp_api.cpp plan_block's
+    tiles and the deal's units of block^2 consecutive sorted positions then straddle two blocks (rp_schedule.h plan_block's
     comment).  What still holds: a permutation, the interleave's count per rank, balanced loads, and most of a rank's
     tiles in whole squares; what does not: every square whole."""
     from rtpotato.dist import deal_tiles

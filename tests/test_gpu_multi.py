@@ -79,15 +79,16 @@ def test_balanced_plan_rebuilds_frame(gpu, world):
 @pytest.mark.parametrize("W,H", [(512, 512), (520, 488)])
 def test_block_deal_matches_restatement(gpu, world, W, H):
     """Scenes dealt in Z-order (tile_order morton, on request: AUTO is the cost order) make balanced plans of square tile blocks
-    (rp_api.cpp plan_block: 4 x 4 here, 4,096 tiles) from the installed cost table: the device plan equals the NumPy
+    (rp_schedule.h plan_block: 4 x 4 here, 4,096 tiles) from the installed cost table: the device plan equals the NumPy
     restatement (rtpotato.dist.deal_tiles with block = 4), and the shards rebuild the interleave frame bit for bit.  The
     520 x 488 grid (65 x 61 tiles) is ragged: its edge blocks hold fewer than block^2 tiles, so later units
-    straddle two blocks (rp_api.cpp plan_block) -- the device must still equal the restatement and rebuild the frame."""
+    straddle two blocks (rp_schedule.h plan_block) -- the device must still equal the restatement and rebuild the frame."""
     import torch
     from rtpotato import _ffi as F
     from rtpotato import scenes
     from rtpotato.dist import deal_tiles, max_slots, shard_params
     from rtpotato.scene import RenderParams, shard_slot_count
+    from test_schedule import plan_block
     sc = scenes.configure(scenes.bunny_full(), W, H)
     p = RenderParams(W, H, 1, 8, scenes.DEFAULT_SEED, 8, 8, shard_map=F.RP_SHARD_BALANCED)
     tx, ty = -(-W // 8), -(-H // 8)
@@ -96,7 +97,8 @@ def test_block_deal_matches_restatement(gpu, world, W, H):
     xs, ys = np.meshgrid(np.arange(tx), np.arange(ty))
     cost = ((50 + 500 * (((xs - 32) ** 2 + (ys - 32) ** 2) < 400)) * rng.uniform(0.8, 1.2, xs.shape)).astype(np.uint32)
     table = np.stack([cost.reshape(-1), cost.reshape(-1) // 4])
-    block = next((b for b in (4, 2) if n >= 32 * world * b * b), 1)  # rp_api.cpp plan_block
+    block = plan_block(p, world)  # rp_schedule.h plan_block, through the host library's hook
+    assert block == next((b for b in (4, 2) if n >= 32 * world * b * b), 1)
     want = deal_tiles(table[0], world, tx, block)
     S = max_slots(p, world)
     gathered = torch.zeros(world * S * 3, dtype=torch.float64, device="cuda")

@@ -144,3 +144,47 @@ def test_learned_unit_order_frame_launch(gpu, sps):
                 rays += int(c[0])
         assert int(ctr[0]) == rays and int(ctr[3]) == 0
         w.close()
+
+
+def test_workspace_regrow_matches_fresh_workspaces(gpu):
+    """One workspace renders a two-batch 64 x 36 frame, a 96 x 54 frame (every reserved buffer grows; the stored unit
+    durations and the learned tile table are the smaller frame's and must not be used), the 64 x 36 frame again (the
+    capacity stays, the stored state is the larger frame's) and a launch of two 64 x 36 frames.  Every result -- colours,
+    foreground, counters -- equals, bit for bit, the same render on a workspace created for it alone (created and
+    destroyed between the steps), and the single-frame steps report a fresh workspace's scheduling flags."""
+    import torch
+    from rtpotato import _ffi as F
+    from rtpotato.scene import shard_slot_count
+    sc, small = _scene("bunny", 64, 36, 40)
+    small = replace(small, samples_per_stream=32, tile_w=16, tile_h=16)  # 40 samples: batches of 32 + 8
+    large = replace(small, width=96, height=54)
+    dev = torch.device("cuda", 0)
+
+    def run(ds, w, p, nf):
+        n = shard_slot_count(p)
+        out = torch.zeros(nf * 3 * n, dtype=torch.float64, device=dev)
+        fg = torch.zeros(nf * n, dtype=torch.float32, device=dev)
+        ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
+        if nf == 1:
+            ds.reserve(p, w)
+            ds.render_device(p, out, ctr, fg=fg, workspace=w)
+        else:
+            ds.reserve_frames(p, nf, w)
+            ds.render_frames_device(p, nf, out, ctr, fg=fg, workspace=w)
+        torch.cuda.synchronize()
+        return out.cpu().numpy().view(np.uint64), fg.cpu().numpy().view(np.uint32), ctr.cpu().numpy(), ds.frame_info(w)
+
+    with gpu.DeviceScene(sc, options={"unit_order": "learned"}) as ds:
+        w = ds.workspace()
+        for step, (p, nf) in enumerate(((small, 1), (large, 1), (small, 1), (small, 2))):
+            got = run(ds, w, p, nf)
+            fresh = ds.workspace()
+            want = run(ds, fresh, p, nf)
+            fresh.close()
+            for g, r in zip(got[:3], want[:3]):
+                assert np.array_equal(g, r), step
+            assert got[2][0] > 0 and got[2][3] == 0, (step, got[2])  # rays traced, no status bit
+            if nf == 1:
+                assert got[3] == want[3] and got[3] & F.RP_FRAME_PROBED and not got[3] & F.RP_FRAME_UNIT_ORDER, (step, got[3])
+        assert got[3] & F.RP_FRAME_UNIT_ORDER  # the two-frame launch ran in the order its lone frame (step 3) learned
+        w.close()

@@ -1,4 +1,4 @@
-"""Host restatement of the per-XCD unit-queue partition (rp_device.h fetch_pixel, rp_api.cpp render_shard):
+"""Host restatement of the per-XCD unit-queue partition (rp_device.h fetch_pixel, rp_schedule.h plan_launch; tests/test_schedule.py checks its chunk choice):
 queue g of G serves the chunks g, g + G, ... of C consecutive tiles of the tile order, nk(g) tiles, its i-th
 tile being (i / C) * G * C + g * C + i % C.  Every tile must be served by exactly one queue, whatever K, G, C
 (the GPU test test_unit_queues_bitwise checks the kernel itself renders identical frames)."""

@@ -263,8 +263,27 @@ static void check_oracle_render(const MeshScene& s) {
   std::printf("oracle render at 1 and 8 threads: identical frames; threaded baseline driver ran\n");
 }
 
+// the render's launch arithmetic (csrc/rp_schedule.h, through the host library's hook): ragged and extreme shapes
+static void check_plan() {
+  rph_launch_plan o;
+  int planned = 0, refused = 0;
+  for (uint32_t w : {1u, 75u, 1920u, 65535u})
+    for (uint32_t tile : {1u, 16u, 32u, 65535u})
+      for (uint32_t spp : {0u, 1u, 40u, 1024u, 0xffffffffu})
+        for (uint32_t nf : {1u, 20u, 64u})
+          for (uint32_t q = 0; q < 4; q++) {
+            const int rc = rph_plan_launch(w, w / 2 + 1, spp, 8, tile, tile, 2, 3, 32, q & 1, nf, q, q, q * 7, 262144, &o);
+            CHECK(rc == RP_OK || rc == RP_EINVAL);
+            if (rc == RP_OK) CHECK(o.queue_chunk >= 1 && o.grid >= 1 && o.n_queue < (1ull << 31));
+            (rc == RP_OK ? planned : refused)++;
+          }
+  CHECK(planned > 0 && refused > 0);
+  std::printf("launch plans: %d planned, %d refused\n", planned, refused);
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
+  check_plan();
   MeshScene a = soup(200000, 11);  // >= 2^16 primitives: the parallel build form (rp_bvh.cpp ParallelBuild) runs
   check_tree("soup", a.desc);
   MeshScene b = grid_with_degenerates(40, 3);
