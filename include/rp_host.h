@@ -98,6 +98,21 @@ int rph_plan_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_
                     uint32_t shard, uint32_t num_shards, uint32_t samples_per_stream, uint32_t shard_map, uint32_t n_frames,
                     uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes, rph_launch_plan* out);
 
+/* Test hook: one round of a draw of the render kernel (raytracing-potato_amd/csrc/rp_draw.h, the same header the
+ * kernel's scatter and camera draws use: window addressing with the ring's mirror tail, the stride, the accept rules,
+ * "first accepted try wins", the position update).  kind: 1 UnitSphere (Lambert), 2 UnitBall (Metal), 3 the
+ * Bernoulli draw's Standard f64 (Dielectric), 4 UnitDisk (camera).  ring_image: a lane's ring exactly as its slab
+ * holds it -- 16 * ring_blocks words (ring_blocks 4 or 8; keystream block b in slot b % ring_blocks), then, for
+ * ring_blocks 8, the tail, the first 8 words of slot 0 again (the ring of 4 has none: 64 words are read, wrapping) --
+ * which must hold every block the round can consume from the even stream word
+ * `pos` on (two tries of 4 words for kinds 1 and 4, of 6 for kind 2; 2 words for kind 3).  On return *accepted tells
+ * whether a try of the round was accepted (always, for kind 3); if so out[0..2] are the values -- the sphere point
+ * (x n, y n, 1 - 2 s), the ball point, the Standard f64 (out[1], out[2] zero), the disk point (out[2] zero) -- and
+ * *new_pos the stream position after the accepted try; if not, *new_pos is the next round's position.  RP_EINVAL
+ * for a bad kind, ring size or odd pos. */
+int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_image, uint32_t pos, double out[3],
+                   uint32_t* new_pos, uint32_t* accepted);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

@@ -13,6 +13,8 @@
 
 #pragma clang fp contract(off)
 
+#include "rp_draw.h"
+
 // Every compile-time knob below changes timing only.  Experiments that change results (timing ablations
 // with wrong streams or colours) are not kept in this file, and a build asking for one is refused so a
 // library that writes wrong frames can never be produced from it.
@@ -194,16 +196,16 @@ RPK_INLINE void seed_key(uint64_t state, uint32_t key[8]) {
 // blocks ahead of every lane).
 //
 // Slab layout per lane (uint4 units): [0,2) key words, [2, 2+4*RING) ring (block b in slot b % RING),
-// [2+4*RING, +8) jitter blocks (block b in slot b & 1).  Per-lane cursors (LDS): end = one past the
-// newest ring block; jtag[2] = block held by each jitter slot.
+// [2+4*RING, +2) the ring's mirror tail (the first 8 words of slot 0 again, so a draw's window reads straight on past
+// the ring's end: rp_draw.h; the ring of 8 blocks only), then 8 of jitter blocks (block b in slot b & 1).  Per-lane cursors (LDS): end = one
+// past the newest ring block; jtag[2] = block held by each jitter slot.
 static constexpr uint32_t RING = 8;  // slab ring capacity; a kernel keeps RngT::ring <= RING blocks ahead
-static constexpr uint32_t SLAB_KEY = 0, SLAB_RING = 2, SLAB_JIT = 2 + 4 * RING;
+static constexpr uint32_t SLAB_KEY = 0, SLAB_RING = 2;  // (the tail and the jitter blocks follow the ring: RngT)
 // The pixel sum and path throughput (6 f64 per lane, read and written at every shade) live in LDS (in the
 // slab: C3 +2.6 %, C5 +4.6 %); the host then keeps ~19 traversal-stack entries in LDS and spills deeper ones to
 // the lane's global run (render_blocks_per_cu picks the split; bunny: 19 of 31, rarely reached).
 // (v43-v47 kept the measured unit's start time in one more uint4 of the slab: 688 B per lane, and C3 wrote 70 GB per
 // frame instead of 56 -- the stamp now lives in its own lane-indexed array, KScene::unit_t0)
-static constexpr uint32_t SLAB_N = SLAB_JIT + 8;
 // A refill pass runs when some lane is at or below RNG_CRIT blocks ahead, or RNG_BATCH lanes have room.
 static constexpr uint32_t RNG_CRIT = 2, RNG_BATCH = 48;
 // Traversal wave-level exits (trav_step): leave the inner-node loop once at most KScene::leaf_break lanes of
@@ -217,8 +219,9 @@ static constexpr uint32_t PRIM_BREAK = 12;
 template <uint32_t RN>
 struct RngT {
   static constexpr uint32_t ring = RN;
-  // a lane's slab for this ring: key, RN ring blocks, 2 jitter blocks (compact: 416 B for RN = 4)
-  static constexpr uint32_t jit = SLAB_RING + 4 * RN, lane_n = jit + 8;
+  // a lane's slab for this ring: key, RN ring blocks, the mirror tail, 2 jitter blocks (704 B; RN = 4: no tail, 416 B)
+  static constexpr uint32_t tail_n = rpd::ring_tail_words(RN) / 4;  // uint4 units
+  static constexpr uint32_t tail = SLAB_RING + 4 * RN, jit = tail + tail_n, lane_n = jit + 8;
   static_assert(RN > RNG_CRIT && RN <= RING && (RN & (RN - 1)) == 0,
                 "ring: a power of two above the critical refill level (a full ring is never refilled), <= RING");
   // a lane stride of 16 B past a 32-B boundary (688 B, v43-v47) made every 64-B block dirty three 32-B sectors: +25 %
@@ -240,6 +243,16 @@ RPK_INLINE void store_block(uint4* dst, const uint32_t w[16]) {
     dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
   }
 }
+// Every store of a ring block goes through here (a lane's own block and an executor's in rng_refill, the in-place
+// fallback gen_block): `tail` is the ring's mirror tail when the block's slot is 0 (ring_tail), else null -- the tail
+// then stays the copy of slot 0's first words that the draw windows rely on.
+RPK_INLINE void store_ring_block(uint4* dst, uint4* tail, const uint32_t w[16]) {
+  store_block(dst, w);
+  if (tail) {
+#pragma unroll
+    for (uint32_t q = 0; q < rpd::TAIL_WORDS / 4; q++) tail[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  }
+}
 RPK_INLINE void load_block(const uint4* src, uint32_t w[16]) {
 #pragma unroll
   for (int q = 0; q < 4; q++) {
@@ -249,6 +262,12 @@ RPK_INLINE void load_block(const uint4* src, uint32_t w[16]) {
 }
 template <uint32_t RN>
 RPK_INLINE uint4* ring_slot(const RngT<RN>& r, uint32_t b) { return r.slab + SLAB_RING + 4 * (b & (RN - 1u)); }
+// the mirror tail of the ring of the lane slab `slab` if it has one and block b lives in slot 0, else null
+// (store_ring_block)
+template <uint32_t RN>
+RPK_INLINE uint4* ring_tail(uint4* slab, uint32_t b) {
+  return RngT<RN>::tail_n != 0 && (b & (RN - 1u)) == 0u ? slab + RngT<RN>::tail : nullptr;
+}
 template <uint32_t RN>
 RPK_INLINE uint4* jit_slot(const RngT<RN>& r, uint32_t b) { return r.slab + RngT<RN>::jit + 4 * (b & 1u); }
 
@@ -319,9 +338,9 @@ RPK_INLINE void rng_refill(RngT<RN>& r, bool alive, bool fresh, uint64_t seed, u
     const uint32_t bb = room ? b : oend + j;
     chacha12(k, bb, w);
     // an executor's block goes into its owner's ring (lane slabs are consecutive within the block)
-    uint4* dst = room ? (main ? ring_slot(r, b) : jit_slot(r, b))
-                      : r.slab + ((int)owner - (int)lane) * (int)RngT<RN>::lane_n + SLAB_RING + 4u * (bb & (RN - 1u));
-    store_block(dst, w);
+    uint4* oslab = r.slab + ((int)owner - (int)lane) * (int)RngT<RN>::lane_n;  // room: owner == lane
+    uint4* dst = room && !main ? jit_slot(r, b) : oslab + SLAB_RING + 4u * (bb & (RN - 1u));
+    store_ring_block(dst, room && !main ? nullptr : ring_tail<RN>(oslab, bb), w);
     if (fresh) store_block(jit_slot(r, 0), w);  // block 0 is also the jitter block of samples 0-3 (render.rs:74-82)
   }
   if (room) {
@@ -334,7 +353,7 @@ RPK_INLINE void rng_refill(RngT<RN>& r, bool alive, bool fresh, uint64_t seed, u
     }
   }
   if (room || served) *r.end = end1 + served;
-  // An executor lane stored blocks into its owner lane's slab above, and the owner reads them through ring_u64 later:
+  // An executor lane stored blocks into its owner lane's slab above, and the owner reads them through ring_window later:
   // a cross-lane hand-off inside one wave.  One wave's memory operations stay in order, and this wavefront-scope fence
   // states the ordering for the memory model; it compiles to no instruction (the kernel's ISA is unchanged).
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -344,12 +363,13 @@ RPK_INLINE void rng_refill(RngT<RN>& r, bool alive, bool fresh, uint64_t seed, u
 // Keystream block b of the lane's key into dst, for the rare draw that finds its block not made yet.  Out
 // of line: the kernel is ~50 KB of code against a 64 KB instruction cache shared by two CUs, and each
 // inlined ChaCha12 is ~2.5 KB that only the fallback paths execute.
-static __device__ __attribute__((noinline, unused)) void gen_block(const uint4* slab, uint32_t b, uint4* dst) {
+// `tail`: ring_tail of a ring block, null for a jitter block.
+static __device__ __attribute__((noinline, unused)) void gen_block(const uint4* slab, uint32_t b, uint4* dst, uint4* tail) {
   const uint4 a = slab[SLAB_KEY], c = slab[SLAB_KEY + 1];
   const uint32_t k[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
   uint32_t w[16];
   chacha12(k, b, w);
-  store_block(dst, w);
+  store_ring_block(dst, tail, w);
 }
 
 template <uint32_t RN>
@@ -357,66 +377,72 @@ RPK_INLINE uint4 rng_jitter(RngT<RN>& r, uint32_t s) {
   const uint32_t b = s >> 2;
   if (r.jtag[(b & 1u) * BLOCK] != b) {
     DREG(DREG_JIT_FALLBACK)
-    gen_block(r.slab, b, jit_slot(r, b));
+    gen_block(r.slab, b, jit_slot(r, b), nullptr);
     r.jtag[(b & 1u) * BLOCK] = b;
   }
   return jit_slot(r, b)[s & 3u];
 }
 
-// rand 0.8 Standard f64: (u64 >> 11) * 2^-53 (exact conversions)
-RPK_INLINE double u64_to_f64(uint64_t u) { return (double)(u >> 11) * (1.0 / 9007199254740992.0); }
-// The same value from the two keystream words, as hi * 2^-32 + (lo >> 11) * 2^-53: both terms and the sum
-// k * 2^-53 (k < 2^53) are exact, so the FMA returns the identical double in 2 cvt + 1 mul + 1 FMA.
-RPK_INLINE double words_f64(uint32_t lo, uint32_t hi) {
-  return __builtin_fma((double)hi, 0x1p-32, (double)(lo >> 11) * 0x1p-53);
-}
-// 2 * words_f64 - 1 (the distributions' `2.0 * r - 1.0`, randomness.rs:24,42,61): 2g = k * 2^-52 is exact and
-// so is k * 2^-52 - 1 (a multiple of 2^-52 of magnitude <= 1), whatever the order -- two exact FMAs.
-RPK_INLINE double words_sym(uint32_t lo, uint32_t hi) {
-  return __builtin_fma((double)hi, 0x1p-31, __builtin_fma((double)(lo >> 11), 0x1p-52, -1.0));
-}
-// Every draw reads the ring directly: the RING blocks of a lane are one circular run of 16*RING words in
-// its slab (L2-resident), so stream word a sits at ring word a % (16*RING) while its block is held
-// (blocks [end - RING, end)).  A draw site makes sure every block it touches is there (ring_ensure:
-// generated in place when the refill pass has not made it yet, rare) and loads its u64 words with one
-// dwordx2 each.  Rejection loops (UnitBall / UnitSphere / UnitDisk) load and evaluate TRIES tries at
-// once and keep the first accepted one -- the draws consumed, and so the stream, are exactly the
-// sequential loop's.  A wave iterates until its slowest lane accepts: with
-// acceptance p a lane needs a geometric number of tries, and the wave's maximum over its ~20 shading lanes
-// is ~5 single tries for the ball (p = pi/6); each round pays one ring-load latency.  (Before, a draw
-// checked its block and the wave copied a 16-word block into LDS whenever any lane crossed one.)
-static constexpr uint32_t TRIES = 2;  // (1 or 3 tries: +0.6 / +0.9 %; 3 or 4 for Metal alone: +0.6 / +1.3 %)
-static_assert((RING & (RING - 1)) == 0, "ring_u64 indexes the ring as 16 * ring words (a power of two)");
-template <uint32_t RN>
-RPK_INLINE uint2 ring_u64(const RngT<RN>& r, uint32_t a) {  // stream words a, a+1 (a even)
-  return reinterpret_cast<const uint2*>(r.slab + SLAB_RING)[(a & (16u * RN - 1u)) >> 1];
-}
-template <uint32_t RN>
-RPK_INLINE double ring_f64(const RngT<RN>& r, uint32_t a) {  // Standard f64
-  const uint2 v = ring_u64(r, a);
-  return words_f64(v.x, v.y);
-}
-template <uint32_t RN>
-RPK_INLINE double ring_sym(const RngT<RN>& r, uint32_t a) {  // 2 * Standard f64 - 1
-  const uint2 v = ring_u64(r, a);
-  return words_sym(v.x, v.y);
+// Every draw reads the ring directly: the RN blocks of a lane are one circular run of 16 RN words in its slab
+// (L2-resident), so stream word a sits at ring word a % (16 RN) while its block is held (blocks [end - RN, end)).
+// A draw site makes sure every block it can consume this round is there (ring_ensure: generated in place when the
+// refill pass has not made it yet, rare) and loads each try's window -- its 2 or 3 consecutive u64 -- with one
+// dwordx4 (and one dwordx2 for a third value) from one address: the ring's mirror tail lets a window that starts in
+// the ring's last words read straight on (rp_draw.h; one masked dwordx2 per value before: C3 and C2 +1.1 %; the ring
+// of 4 blocks keeps those loads and has no tail: with one, C5 lost 0.6 %).  The rejection
+// loops (UnitBall / UnitSphere / UnitDisk) load and evaluate TRIES tries at once and keep the first accepted one --
+// the draws consumed, and so the stream, are exactly the sequential loop's (rpd::draw_pick).  A wave iterates until
+// its slowest lane accepts: with acceptance p a lane needs a geometric number of tries, and the wave's maximum over its
+// ~20 shading lanes is ~5 single tries for the ball (p = pi/6); each round pays one ring-load latency.
+using rpd::TRIES;
+static_assert((RING & (RING - 1)) == 0, "the ring is indexed as 16 * ring words (a power of two)");
+typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));  // a window starts on an even word
+template <uint32_t STRIDE, uint32_t RN>
+RPK_INLINE void ring_window(const RngT<RN>& r, uint32_t a, rpd::Try& t) {  // stream words a .. a + STRIDE - 1
+  t.w[4] = 0; t.w[5] = 0;
+  if constexpr (RngT<RN>::tail_n != 0) {
+    const char* p = reinterpret_cast<const char*>(r.slab + SLAB_RING) + 4u * rpd::value_word(a, 0, RN);
+    const u32x4_a8 v = *reinterpret_cast<const u32x4_a8*>(p);
+    t.w[0] = v.x; t.w[1] = v.y; t.w[2] = v.z; t.w[3] = v.w;
+    if (STRIDE == 6u) {
+      const uint2 z = *reinterpret_cast<const uint2*>(p + 16);
+      t.w[4] = z.x; t.w[5] = z.y;
+    }
+  } else {  // no tail: one wrapped dwordx2 per value
+    const uint2* ring = reinterpret_cast<const uint2*>(r.slab + SLAB_RING);
+#pragma unroll
+    for (uint32_t k = 0; k < STRIDE / 2u; k++) {
+      const uint2 v = ring[rpd::value_word(a, k, RN) >> 1];
+      t.w[2 * k] = v.x; t.w[2 * k + 1] = v.y;
+    }
+  }
 }
 template <uint32_t RN>
 RPK_INLINE void ring_ensure(RngT<RN>& r, uint32_t last_blk) {
   while (last_blk >= *r.end) {
     DREG(DREG_RNG_FALLBACK)
     const uint32_t b = *r.end;
-    gen_block(r.slab, b, ring_slot(r, b));
+    gen_block(r.slab, b, ring_slot(r, b), ring_tail<RN>(r.slab, b));
     *r.end = b + 1;
   }
 }
-// One Standard f64 draw (rand 0.8 gen::<f64>, two stream words)
+// One round of a rejection sampler at stream word a: its blocks made sure of, the tries' windows loaded (try j at
+// a + STRIDE j) and evaluated.  True when a try was accepted: q is it, and r.pos the position after it.
+template <uint32_t STRIDE, uint32_t RN>
+RPK_INLINE bool ring_round(RngT<RN>& r, uint32_t a, rpd::Draw& q) {
+  ring_ensure(r, rpd::round_last_block(a, STRIDE));
+  rpd::Try t[TRIES];
+#pragma unroll
+  for (uint32_t j = 0; j < TRIES; j++) ring_window<STRIDE>(r, a + STRIDE * j, t[j]);
+  return rpd::draw_pick(STRIDE, a, t, q, r.pos);
+}
+// One Standard f64 draw (rand 0.8 gen::<f64>): the u64 at the window address of r.pos
 template <uint32_t RN>
 RPK_INLINE double gen_f64(RngT<RN>& r) {
   ring_ensure(r, r.pos >> 4);
-  const double x = ring_f64(r, r.pos);
+  const uint2 v = reinterpret_cast<const uint2*>(r.slab + SLAB_RING)[rpd::window_word(r.pos, RN) >> 1];
   r.pos += 2;
-  return x;
+  return rpd::words_unit(v.x, v.y);
 }
 
 // ------------------------------------------------------------------ math -------------------------
@@ -1235,53 +1261,26 @@ RPK_INLINE bool scatter_eval(const rpl::Material& m, V3 d, const Surf& h, R& rng
     case 1: {  // Lambert (material.rs:115-130)
       DREG(DREG_LAMBERT)
       if (dot(h.n, d) > 0.0) return false;
-      double x = 0.0, y = 0.0, s = 0.0;
-      // UnitSphere (randomness.rs:58-73): tries of 2 draws, TRIES per round (see ring_ensure)
+      // UnitSphere (randomness.rs:58-73): tries of 2 draws, TRIES per round (see ring_round)
+      rpd::Draw q;
       for (uint32_t a = rng.pos;; a += 4u * TRIES) {
         DREG(DREG_LOOP_LAMBERT)
-        ring_ensure(rng, (a + 4u * TRIES - 1u) >> 4);
-        double tx[TRIES], ty[TRIES];
-#pragma unroll
-        for (int j = 0; j < TRIES; j++) {
-          tx[j] = ring_sym(rng, a + 4u * j);
-          ty[j] = ring_sym(rng, a + 4u * j + 2u);
-        }
-        bool done = false;
-#pragma unroll
-        for (int j = TRIES - 1; j >= 0; j--) {  // the first accepted try wins
-          const double qx = tx[j], qy = ty[j], qs = qx * qx + qy * qy;
-          if (qs < 1.0) { x = qx; y = qy; s = qs; rng.pos = a + 4u * (j + 1); done = true; }
-        }
-        if (done) break;
+        if (ring_round<4u>(rng, a, q)) break;
       }
-      const double q = 2.0 * sqrt(1.0 - s);
-      nd = normalize(add(h.n, v3(x * q, y * q, 1.0 - 2.0 * s)));
+      const double f = 2.0 * sqrt(1.0 - q.s);
+      nd = normalize(add(h.n, v3(q.x * f, q.y * f, 1.0 - 2.0 * q.s)));
       return true;
     }
     case 2: {  // Metal (material.rs:132-152)
       DREG(DREG_METAL)
       if (dot(h.n, d) > 0.0) return false;
-      double x = 0.0, y = 0.0, z = 0.0;
-      // UnitBall (randomness.rs:39-53): tries of 3 draws, TRIES per round (see ring_ensure)
+      // UnitBall (randomness.rs:39-53): tries of 3 draws, TRIES per round (see ring_round)
+      rpd::Draw q;
       for (uint32_t a = rng.pos;; a += 6u * TRIES) {
         DREG(DREG_LOOP_METAL)
-        ring_ensure(rng, (a + 6u * TRIES - 1u) >> 4);
-        double tx[TRIES], ty[TRIES], tz[TRIES];
-#pragma unroll
-        for (int j = 0; j < TRIES; j++) {
-          tx[j] = ring_sym(rng, a + 6u * j);
-          ty[j] = ring_sym(rng, a + 6u * j + 2u);
-          tz[j] = ring_sym(rng, a + 6u * j + 4u);
-        }
-        bool done = false;
-#pragma unroll
-        for (int j = TRIES - 1; j >= 0; j--) {  // the first accepted try wins
-          const double qx = tx[j], qy = ty[j], qz = tz[j];
-          if ((qx * qx + qy * qy) + qz * qz < 1.0) { x = qx; y = qy; z = qz; rng.pos = a + 6u * (j + 1); done = true; }
-        }
-        if (done) break;
+        if (ring_round<6u>(rng, a, q)) break;
       }
-      const V3 r = normalize(add(reflect(d, h.n), smul(m.scatter_param, v3(x, y, z))));
+      const V3 r = normalize(add(reflect(d, h.n), smul(m.scatter_param, v3(q.x, q.y, q.z))));
       if (dot(h.n, r) < 0.0) return false;
       nd = r;
       return true;
@@ -1651,26 +1650,14 @@ RPK_INLINE void start_sample(R& rng, uint32_t s, uint32_t pi, uint32_t pj, V3& o
   KArgsPtr A = kargs();
   const uint4 jw = rng_jitter(rng, s);
   const uint32_t w0 = jw.x, w1 = jw.y, w2 = jw.z, w3 = jw.w;
-  const double ju = ((double)pi + words_f64(w0, w1)) / (double)A->P.W;
-  const double jv = ((double)pj + words_f64(w2, w3)) / (double)A->P.H;
-  double dx = 0.0, dy = 0.0;
-  // UnitDisk (randomness.rs:21-34): tries of 2 draws, TRIES per round (see ring_ensure)
+  const double ju = ((double)pi + rpd::words_unit(w0, w1)) / (double)A->P.W;
+  const double jv = ((double)pj + rpd::words_unit(w2, w3)) / (double)A->P.H;
+  // UnitDisk (randomness.rs:21-34): tries of 2 draws, TRIES per round (see ring_round)
+  rpd::Draw q;
   for (uint32_t a = rng.pos;; a += 4u * TRIES) {
-    ring_ensure(rng, (a + 4u * TRIES - 1u) >> 4);
-    double tx[TRIES], ty[TRIES];
-#pragma unroll
-    for (int j = 0; j < TRIES; j++) {
-      tx[j] = ring_sym(rng, a + 4u * j);
-      ty[j] = ring_sym(rng, a + 4u * j + 2u);
-    }
-    bool done = false;
-#pragma unroll
-    for (int j = TRIES - 1; j >= 0; j--) {  // the first accepted try wins
-      const double qx = tx[j], qy = ty[j];
-      if (qx * qx + qy * qy < 1.0) { dx = qx; dy = qy; rng.pos = a + 4u * (j + 1); done = true; }
-    }
-    if (done) break;
+    if (ring_round<4u>(rng, a, q)) break;
   }
+  const double dx = q.x, dy = q.y;
   camera_dir(kargs(), ju, jv, dx, dy, o, d);
 }
 

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rp_bvh.h"
+#include "rp_draw.h"
 #include "rp_kernel.h"
 #include "rp_schedule.h"
 
@@ -737,6 +738,44 @@ int rph_make_div32(uint32_t d, uint32_t* m, uint32_t* s) {
   const rpk::Div32 v = rpk::make_div32(d);
   *m = v.m;
   *s = v.s;
+  return RP_OK;
+}
+
+int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_image, uint32_t pos, double out[3],
+                   uint32_t* new_pos, uint32_t* accepted) {
+  if (kind < rpd::DRAW_SPHERE || kind > rpd::DRAW_DISK || (ring_blocks != 4 && ring_blocks != 8) || (pos & 1u) ||
+      !ring_image || !out || !new_pos || !accepted)
+    return fail("rph_draw_round: kind 1-4, ring_blocks 4 or 8, even pos, non-NULL pointers");
+  out[0] = out[1] = out[2] = 0.0;
+  if (kind == rpd::DRAW_UNIFORM) {  // the kernel's gen_f64: the u64 at the window address
+    const uint32_t* p = ring_image + rpd::window_word(pos, ring_blocks);
+    out[0] = rpd::words_unit(p[0], p[1]);
+    *new_pos = pos + 2u;
+    *accepted = 1u;
+    return RP_OK;
+  }
+  const uint32_t stride = rpd::draw_stride(kind);
+  rpd::Try t[rpd::TRIES];
+  for (uint32_t j = 0; j < rpd::TRIES; j++) {  // the kernel's ring_window
+    for (uint32_t q = 0; q < rpd::WINDOW_WORDS; q++) t[j].w[q] = 0u;
+    for (uint32_t k = 0; k < stride / 2u; k++) {
+      const uint32_t* p = ring_image + rpd::value_word(pos + stride * j, k, ring_blocks);
+      t[j].w[2 * k] = p[0];
+      t[j].w[2 * k + 1] = p[1];
+    }
+  }
+  rpd::Draw d{0.0, 0.0, 0.0, 0.0};
+  uint32_t np = pos + stride * rpd::TRIES;
+  *accepted = rpd::draw_pick(stride, pos, t, d, np) ? 1u : 0u;
+  *new_pos = np;
+  if (*accepted) {
+    if (kind == rpd::DRAW_SPHERE) {  // the Lambert site's point (rp_device.h scatter_eval)
+      const double f = 2.0 * std::sqrt(1.0 - d.s);
+      out[0] = d.x * f; out[1] = d.y * f; out[2] = 1.0 - 2.0 * d.s;
+    } else {
+      out[0] = d.x; out[1] = d.y; out[2] = d.z;
+    }
+  }
   return RP_OK;
 }
 

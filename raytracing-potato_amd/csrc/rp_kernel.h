@@ -24,14 +24,15 @@ struct KScene {
   uint32_t stack_depth;  // traversal stack entries per lane (3 x max_depth + 7)
   uint32_t lds_depth;    // entries of it in LDS; entries [lds_depth, stack_depth) spill to `spill`
   uint64_t* diag;        // diagnostic counters (RPK_DIAG builds), DIAG_N x u64
-  uint32_t* rng_slab;    // per-lane keystream cache, render_lanes x rng_slab_bytes_per_lane() bytes
+  uint32_t* rng_slab;    // per-lane keystream cache, render_lanes x rng_slab_bytes_per_lane(node_format) bytes
   uint32_t* spill;       // per-lane stack overflow, render_lanes x (stack_depth - lds_depth) entries
   uint32_t* unit_t0;     // per-lane start time of the lane's measured unit (tile costs), render_lanes words
 };
 
-// Bytes of keystream cache (ChaCha key, ring of main-stream blocks, jitter blocks) per resident lane of
-// the render kernel; the render grid never exceeds the lanes the slab was sized for.
-uint64_t rng_slab_bytes_per_lane();
+// Bytes of keystream cache (ChaCha key, ring of main-stream blocks and its mirror tail, jitter blocks) per resident
+// lane of the render kernel of a node format (rp_device.h RngT::lane_n: 704 B with the ring of 8 blocks, 416 B with
+// the q8 kernel's 4, which has no tail); the render grid never exceeds the lanes the slab was sized for.
+uint64_t rng_slab_bytes_per_lane(uint32_t node_format);
 enum { RENDER_BLOCK = 64 };
 
 // Diagnostic counters (RPK_DIAG builds): wave-cycles per phase {fetch, new sample, traverse, shade,

@@ -758,7 +758,12 @@ int launch_learn_costs(const uint32_t* sum, const uint32_t* max, uint32_t rank_s
   return (int)hipGetLastError();
 }
 
-uint64_t rng_slab_bytes_per_lane() { return (uint64_t)SLAB_N * sizeof(uint4); }
+uint64_t rng_slab_bytes_per_lane(uint32_t nf) {  // the lane stride of the kernel that renders node format nf
+  const uint32_t n = nf == rpl::NODES_Q8   ? RngT<RingFor<rpl::NODES_Q8>>::lane_n
+                     : nf == rpl::NODES_W8 ? RngT<RingFor<rpl::NODES_W8>>::lane_n
+                                           : RngT<RingFor<rpl::NODES_F32>>::lane_n;
+  return (uint64_t)n * sizeof(uint4);
+}
 
 int render_blocks_per_cu(uint32_t lds_depth, bool spill, uint32_t nf, int* blocks) {
   const size_t lds = (size_t)lds_depth * BLOCK * sizeof(uint32_t);

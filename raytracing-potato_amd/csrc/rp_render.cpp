@@ -16,7 +16,7 @@ int ws_alloc(rp_scene* s, rp_workspace* w) {
       !w->d_tile_cost.alloc(2 * rpk::TILE_SORT_MAX) || !w->d_tile_order.alloc(rpk::TILE_SORT_MAX) ||
       !w->d_plan.alloc(2 * rpk::TILE_SORT_MAX + 2) || !w->d_meas.alloc(2 * rpk::TILE_SORT_MAX) ||
       !w->d_fcost.alloc(2 * rpk::TILE_SORT_MAX) || !w->d_sort.alloc(rpk::SORT_SCRATCH) ||
-      !w->d_slab.alloc(lanes * rpk::rng_slab_bytes_per_lane()) ||
+      !w->d_slab.alloc(lanes * rpk::rng_slab_bytes_per_lane(s->ks.node_format)) ||
       !w->d_spill.alloc(lanes * std::max<uint64_t>(1, s->ks.stack_depth - s->ks.lds_depth)) || !w->d_t0.alloc(lanes) ||
       hipEventCreateWithFlags(w->ev_gathered.put(), hipEventDisableTiming) != hipSuccess)
     return fail(RP_ENOMEM, "hipMalloc render workspace");  // (the workspace's owner frees what was allocated)
