@@ -113,6 +113,14 @@ int rph_plan_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_
 int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_image, uint32_t pos, double out[3],
                    uint32_t* new_pos, uint32_t* accepted);
 
+/* Test hook: how a ray enters the conservative f32 box test (raytracing-potato_amd/csrc/rp_ray.h, the same header the
+ * kernels' setup_ray32 and trav_step use, except that the reciprocal is a correctly rounded 1 / x here).  rays: n x 8
+ * {o, d, t_min, best}, as rph_bvh_traversal_stats takes them; node_format RP_NODES_F32, _Q8 or _W8 (the quantized
+ * formats add their frame term, with qbound the scene's bound on every frame's |o| and 255 s).  out: n x 11 floats
+ * {inv[3], nb[3], fb[3], tmin32, best32}: per axis the clamped slope and the near- and far-plane addends,
+ * nb <= -oinv - D and fb >= -oinv + D; tmin32 <= t_min; best32 >= best (+inf for best = +inf). */
+int rph_ray_setup(uint32_t node_format, double qbound, const double* rays, uint64_t n, float* out);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

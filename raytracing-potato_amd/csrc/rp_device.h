@@ -14,6 +14,7 @@
 #pragma clang fp contract(off)
 
 #include "rp_draw.h"
+#include "rp_ray.h"
 
 // Every compile-time knob below changes timing only.  Experiments that change results (timing ablations
 // with wrong streams or colours) are not kept in this file, and a build asking for one is refused so a
@@ -82,6 +83,15 @@ __shared__ unsigned long long g_dcyc[DCYC_N];
 static constexpr int BLOCK = RENDER_BLOCK;
 typedef float f2 __attribute__((ext_vector_type(2)));
 RPK_INLINE f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+// min(t, best32) for a t that is not NaN (a slab t^: finite, rp_device.h "conservative f32 box test") and
+// best32 = rpr::best_above(..), whose sign bit is clear: the signed-integer order of the bit patterns is then the
+// floats' order (a negative t is a negative integer, below every best32; two non-negative floats order as their
+// patterns), so v_min_i32 returns the same float as v_min_f32 -- without the v_max_f32 x, x the compiler puts in
+// front of a float min to quiet a value it cannot prove canonical (best32 comes from integer arithmetic, once per
+// step, and the quieting was redone at every node visit).
+RPK_INLINE float min_best(float t, float best32) {
+  return __int_as_float(min(__float_as_int(t), __float_as_int(best32)));
+}
 static constexpr uint32_t STACK_SLACK = 3;  // spare LDS stack entries for the branchless push (writes reach sp+2 <= cap+2)
 static constexpr double RAY_EPSILON = 1e-3;  // utility.rs:30
 static constexpr double SMOL = 1e-7;         // utility.rs:31
@@ -511,10 +521,14 @@ struct TravDiag {
 // The single-rounding form fma(P, inv, -oinv) errs by <= 5u |t| + |o_ray - o32| |inv| (1 + 6u) + u |o32 inv|
 // against the exact t = (P - o_ray) / d (u = 2^-24); with every |o| and |q s| <= qbound (rp_layout.h),
 // |e| <= u (1 + u) |inv| (2 qbound + |o32|) + u^2 |o32 inv|, and e = 0 when inv = +-2^64 (the clamp below)
-// and o32 = 0 (A and B exact).  Call D_a the absolute terms of axis a.  Each axis's planes are moved
-// outward by its own D_a, folded into the FMA's addend: near planes use nb_a = fl_down(-oinv_a - D_a), far
-// planes fb_a = fl_up(-oinv_a + D_a) (Node4Q: B_near = fma(o, inv, nb_a), B_far = fma(o, inv, fb_a), whose
-// roundings the frame term covers).  A box whose exact interval meets [t_min, best] at some t* > 0 then has
+// and o32 = 0 (A and B exact).  Call E_a the absolute terms of axis a.  Each axis's planes are moved
+// outward by its own D_a >= E_a, folded into the FMA's addend: near planes use an nb_a <= -oinv_a - D_a, far
+// planes an fb_a >= -oinv_a + D_a (Node4Q: B_near = fma(o, inv, nb_a), B_far = fma(o, inv, fb_a), whose
+// roundings the frame term covers), and the ray's interval enters as tmin32 <= t_min and best32 >= best.  These five
+// inequalities are all the argument uses; rp_ray.h makes the values and shows they hold: D_a in f64, the addends and
+// tmin32 by rounding to nearest and one unconditional step outward (at most one float wider than the exact directed
+// rounding, a third of its instructions), best32 by a three-instruction form that keeps +inf.  A wider addend only
+// passes more boxes.  A box whose exact interval meets [t_min, best] at some t* > 0 then has
 // every near plane <= t*(1 + 6u) (those behind the origin or below tmin32 <= t* do not raise t_near) and
 // every far plane >= t*(1 - 6u), so the test
 //     fma(tnear^, 1 - 2^-19, -2^-100) <= tfar^
@@ -527,9 +541,9 @@ struct TravDiag {
 // COORD_MAX), so every A, B and t^ is finite; an A that underflows errs by < 2^-118, inside the 2^-100 term.
 struct Ray32 {
   float ix, iy, iz;     // rcp(fl(d))
-  float nbx, nby, nbz;  // near-plane addends fl_down(-oinv - D) per axis
-  float fbx, fby, fbz;  // far-plane addends fl_up(-oinv + D) per axis
-  float tmin;           // t_min rounded down
+  float nbx, nby, nbz;  // near-plane addends <= -oinv - D per axis (rp_ray.h)
+  float fbx, fby, fbz;  // far-plane addends >= -oinv + D per axis
+  float tmin;           // <= t_min
   uint32_t sx, sy, sz;  // per axis, by the sign of the slope: Node4 = byte offset of the near plane row
                         // (lo_* or hi_*; the far row is the other); Node4Q/Node8Q = v_perm_b32 selector picking
                         // the near plane codes out of the {hi, lo} word pair (the far codes out of {lo, hi})
@@ -543,51 +557,17 @@ RPK_INLINE uint32_t dir_octant(V3 d) {
          (uint32_t)(__double_as_longlong(d.z) < 0) << 2;
 }
 
-// next representable float towards +inf / -inf (finite inputs; the callers only step values that
-// rounded the wrong way, which are finite)
-RPK_INLINE float next_up(float f) {
-  const int32_t b = __float_as_int(f);
-  if (f == 0.0f) return __int_as_float(1);
-  return __int_as_float(f > 0.0f ? b + 1 : b - 1);
-}
-RPK_INLINE float next_down(float f) { return -next_up(-f); }
-RPK_INLINE float f32_down(double x) {
-  const float f = (float)x;
-  return (double)f > x ? next_down(f) : f;
-}
-RPK_INLINE float f32_up(double x) {
-  const float f = (float)x;
-  return (double)f < x ? next_up(f) : f;
-}
-
+// The per-axis slopes and addends, tmin32 and best32 are rp_ray.h's (shared with the host: the inequalities they keep
+// and the argument are written there).
 template <uint32_t NF>
 RPK_INLINE void setup_ray32(V3 o, V3 d, double tmin, double qbound, Ray32& r) {
-  const float ox = (float)o.x, oy = (float)o.y, oz = (float)o.z;
-  // |inv| clamped to 2^64: a zero direction component gives a huge finite slope instead of inf, so the
-  // fma form never forms inf - inf; the slack term |o - o32| |inv| still covers an origin that rounded
-  // across a slab plane, and a slab the ray never reaches still yields a huge t (a miss), as in f64.
-  r.ix = fminf(fmaxf(__builtin_amdgcn_rcpf((float)d.x), -0x1p64f), 0x1p64f);
-  r.iy = fminf(fmaxf(__builtin_amdgcn_rcpf((float)d.y), -0x1p64f), 0x1p64f);
-  r.iz = fminf(fmaxf(__builtin_amdgcn_rcpf((float)d.z), -0x1p64f), 0x1p64f);
-  const float oix = ox * r.ix, oiy = oy * r.iy, oiz = oz * r.iz;
-  // |o - o32| is exact in f64 (Sterbenz); an axis with no origin rounding contributes no origin term
-  const double ex = fabs(o.x - (double)ox), ey = fabs(o.y - (double)oy), ez = fabs(o.z - (double)oz);
-  const double k = 1.0 + 0x1p-20, u = 0x1p-23, q2 = 2.0 * qbound;
-  const auto fr = [&](float inv, float o32) {  // the Node4Q frame term e (see above)
-    return (NF == rpl::NODES_F32 || (fabsf(inv) == 0x1p64f && o32 == 0.0f))
-               ? 0.0
-               : fabs((double)inv) * (q2 + fabs((double)o32)) * u * k;
-  };
-  const double Dx = ((ex == 0.0 ? 0.0 : ex * fabs((double)r.ix) * k) + fabs((double)oix) * u + fr(r.ix, ox)) * k;
-  const double Dy = ((ey == 0.0 ? 0.0 : ey * fabs((double)r.iy) * k) + fabs((double)oiy) * u + fr(r.iy, oy)) * k;
-  const double Dz = ((ez == 0.0 ? 0.0 : ez * fabs((double)r.iz) * k) + fabs((double)oiz) * u + fr(r.iz, oz)) * k;
-  r.nbx = f32_down(-(double)oix - Dx);
-  r.nby = f32_down(-(double)oiy - Dy);
-  r.nbz = f32_down(-(double)oiz - Dz);
-  r.fbx = f32_up(-(double)oix + Dx);
-  r.fby = f32_up(-(double)oiy + Dy);
-  r.fbz = f32_up(-(double)oiz + Dz);
-  r.tmin = f32_down(tmin);
+  constexpr bool FRAME = NF != rpl::NODES_F32;
+  const rpr::Axis ax = rpr::axis_setup<FRAME>(o.x, d.x, qbound), ay = rpr::axis_setup<FRAME>(o.y, d.y, qbound),
+                  az = rpr::axis_setup<FRAME>(o.z, d.z, qbound);
+  r.ix = ax.inv; r.iy = ay.inv; r.iz = az.inv;
+  r.nbx = ax.nb; r.nby = ay.nb; r.nbz = az.nb;
+  r.fbx = ax.fb; r.fby = ay.fb; r.fbz = az.fb;
+  r.tmin = rpr::f32_below(tmin);
   r.oct = dir_octant(d);
   if (NF != rpl::NODES_F32) {
     r.sx = r.ix < 0.0f ? 0x07060504u : 0x03020100u;
@@ -767,7 +747,7 @@ RPK_INLINE void trav_step_w8(const KScene& S, lds_u32* stk, uint32_t stride, uin
                              V3 d, double tmin, TravState& ts, bool& overflow, TravDiag* td, uint32_t* work) {
   uint32_t gx = ts.cur, gy = ts.gy, px = ts.leaf, py = ts.py, sp = ts.sp;
   double best = ts.best;
-  float best32 = f32_up(best);
+  const float best32 = rpr::best_above(best);
   const uint32_t cap = S.stack_depth - STACK_SLACK;  // words
   auto push = [&](uint32_t x, uint32_t y) {
     if (sp + 2u > cap) { overflow = true; return; }  // cannot happen for a stack sized from the tree depth
@@ -819,7 +799,7 @@ RPK_INLINE void trav_step_w8(const KScene& S, lds_u32* stk, uint32_t stride, uin
 #pragma unroll
         for (int e = 0; e < 2; e++) {
           TN[e] = fmaxf(fmaxf(NX[e], NY[e]), fmaxf(NZ[e], r.tmin));
-          TF[e] = fminf(fminf(FX[e], FY[e]), fminf(FZ[e], best32));
+          TF[e] = min_best(fminf(fminf(FX[e], FY[e]), FZ[e]), best32);
         }
         const f2 lhs = pk_fma(TN, f2{1.0f - 0x1p-19f, 1.0f - 0x1p-19f}, f2{-0x1p-100f, -0x1p-100f});
 #pragma unroll
@@ -880,7 +860,7 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
   }
   uint32_t cur = ts.cur, sp = ts.sp, leaf = ts.leaf;
   double best = ts.best;
-  float best32 = f32_up(best);
+  const float best32 = rpr::best_above(best);
   const uint32_t cap = S.stack_depth - STACK_SLACK;
   DCYC_BEGIN(cnode)
   // ---- inner nodes
@@ -945,6 +925,7 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
       FZ[0] = pk_fma(f2{fz.x, fz.y}, iz, fbz); FZ[1] = pk_fma(f2{fz.z, fz.w}, iz, fbz);
     }
     float tn[4];
+    uint32_t n_hit = 0u;  // counted from the four test masks: off the sort's dependent chain
     uint32_t cc[4] = {ch.x, ch.y, ch.z, ch.w};
     f2 TN[2], TF[2];
 #pragma unroll
@@ -952,7 +933,7 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
 #pragma unroll
       for (int e = 0; e < 2; e++) {
         TN[q][e] = fmaxf(fmaxf(NX[q][e], NY[q][e]), fmaxf(NZ[q][e], r.tmin));
-        TF[q][e] = fminf(fminf(FX[q][e], FY[q][e]), fminf(FZ[q][e], best32));
+        TF[q][e] = min_best(fminf(fminf(FX[q][e], FY[q][e]), FZ[q][e]), best32);
       }
       // fma(tnear, 1 - 2^-19, -2^-100) <= tfar (section 4.2 of DESIGN.md): one packed FMA per pair
       const f2 lhs = pk_fma(TN[q], f2{1.0f - 0x1p-19f, 1.0f - 0x1p-19f}, f2{-0x1p-100f, -0x1p-100f});
@@ -961,6 +942,7 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
         const int c = 2 * q + e;
         const bool hit = lhs[e] <= TF[q][e] && (NF != rpl::NODES_Q8 || cc[c] != rpl::ENTRY_EMPTY);
         tn[c] = hit ? TN[q][e] : __builtin_huge_valf();
+        n_hit += hit ? 1u : 0u;
       }
     }
     // sort (tn, entry) ascending: misses (+inf) go last
@@ -976,12 +958,10 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
 }
     RPK_CSWAP(0, 1) RPK_CSWAP(2, 3) RPK_CSWAP(0, 2) RPK_CSWAP(1, 3) RPK_CSWAP(1, 2)
 #undef RPK_CSWAP
-    // The hits are a prefix of the sorted entries (misses sort last as +inf).  Push the k = hits - 1
+    // The hits are a prefix of the sorted entries (misses sort last as +inf; a hit's key is finite, so n_hit -- the
+    // number of test masks set -- is the number of keys that are not +inf).  Push the k = hits - 1
     // farther ones far-to-near without branches: slots sp..sp+2 are written unconditionally (the stack
     // has STACK_SLACK spare entries; slots past the new top are garbage) and sp advances by k.
-    const float INFF = __builtin_huge_valf();
-    const uint32_t n_hit = (uint32_t)(tn[0] != INFF) + (uint32_t)(tn[1] != INFF) + (uint32_t)(tn[2] != INFF) +
-                           (uint32_t)(tn[3] != INFF);
     const uint32_t k = n_hit > 1u ? n_hit - 1u : 0u;
     const uint32_t e0 = k == 3u ? cc[3] : (k == 2u ? cc[2] : cc[1]), e1 = k == 3u ? cc[2] : cc[1];
     // Whether every lane's pushes and pops of this visit stay in the LDS part of its stack: a wave-uniform branch

@@ -15,6 +15,7 @@
 #include "rp_bvh.h"
 #include "rp_draw.h"
 #include "rp_kernel.h"
+#include "rp_ray.h"
 #include "rp_schedule.h"
 
 namespace {
@@ -438,29 +439,20 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
   if (rc != RP_OK) return fail(err);
   const bool q8 = ps.node_format != rpl::NODES_F32;  // Node4Q or Node8Q: the frame term
   const bool w8 = ps.node_format == rpl::NODES_W8;
-  auto down = [](double x) { float f = (float)x; if ((double)f > x) f = std::nextafter(f, -INFINITY); return f; };
-  auto up = [](double x) { float f = (float)x; if ((double)f < x) f = std::nextafter(f, INFINITY); return f; };
   for (uint64_t r = 0; r < n; r++) {
     const double* q = rays + 8 * r;
     const double o[3] = {q[0], q[1], q[2]}, d[3] = {q[3], q[4], q[5]};
     const double tmin = q[6];
-    float inv[3], nb[3], fb[3];  // per axis: slope, near- and far-plane addends (rp_device.h setup_ray32)
+    float inv[3], nb[3], fb[3];  // per axis: slope, near- and far-plane addends (rp_ray.h, as rp_device.h setup_ray32)
     for (int k = 0; k < 3; k++) {
-      const float o32 = (float)o[k];
-      inv[k] = std::fmin(std::fmax(1.0f / (float)d[k], -0x1p64f), 0x1p64f);
-      const float oinv = o32 * inv[k];
-      const double e = std::fabs(o[k] - (double)o32);
-      const double Dk = ((e == 0.0 ? 0.0 : e * std::fabs((double)inv[k]) * (1.0 + 0x1p-20)) + std::fabs((double)oinv) * 0x1p-23 +
-                         ((!q8 || (std::fabs(inv[k]) == 0x1p64f && o32 == 0.0f))
-                              ? 0.0
-                              : std::fabs((double)inv[k]) * (2.0 * ps.qbound + std::fabs((double)o32)) * 0x1p-23 * (1.0 + 0x1p-20))) *
-                        (1.0 + 0x1p-20);
-      nb[k] = down(-(double)oinv - Dk);
-      fb[k] = up(-(double)oinv + Dk);
+      const rpr::Axis a = q8 ? rpr::axis_setup<true>(o[k], d[k], ps.qbound) : rpr::axis_setup<false>(o[k], d[k], 0.0);
+      inv[k] = a.inv;
+      nb[k] = a.nb;
+      fb[k] = a.fb;
     }
-    const float tmin32 = down(tmin);
+    const float tmin32 = rpr::f32_below(tmin);
     double best = q[7];
-    float best32 = up(best);
+    float best32 = rpr::best_above(best);
     int64_t bestp = -1;
     uint64_t visits = 0, tests = 0;
     auto test = [&](uint32_t k) {
@@ -500,7 +492,7 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
         best = t;
         bestp = ps.prim_refs[k].src;
       }
-      best32 = up(best);
+      best32 = rpr::best_above(best);
     };
     // the always-tested primitives first (rp_bvh.h BuildOptions::always_max), as the kernel does
     for (uint32_t k = ps.always_first; k < ps.always_first + ps.n_always; k++) test(k);
@@ -738,6 +730,26 @@ int rph_make_div32(uint32_t d, uint32_t* m, uint32_t* s) {
   const rpk::Div32 v = rpk::make_div32(d);
   *m = v.m;
   *s = v.s;
+  return RP_OK;
+}
+
+int rph_ray_setup(uint32_t node_format, double qbound, const double* rays, uint64_t n, float* out) {
+  if ((node_format != RP_NODES_F32 && node_format != RP_NODES_Q8 && node_format != RP_NODES_W8) || !(qbound >= 0.0) ||
+      (n && (!rays || !out)))
+    return fail("rph_ray_setup: node_format f32, q8 or w8, qbound >= 0, non-NULL pointers");
+  const bool frame = node_format != RP_NODES_F32;
+  for (uint64_t r = 0; r < n; r++) {
+    const double* q = rays + 8 * r;
+    float* o = out + 11 * r;
+    for (int k = 0; k < 3; k++) {
+      const rpr::Axis a = frame ? rpr::axis_setup<true>(q[k], q[3 + k], qbound) : rpr::axis_setup<false>(q[k], q[3 + k], qbound);
+      o[k] = a.inv;
+      o[3 + k] = a.nb;
+      o[6 + k] = a.fb;
+    }
+    o[9] = rpr::f32_below(q[6]);
+    o[10] = rpr::best_above(q[7]);
+  }
   return RP_OK;
 }
 

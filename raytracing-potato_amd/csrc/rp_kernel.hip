@@ -65,7 +65,8 @@ __global__ void __launch_bounds__(BLOCK) RPK_RENDER_ATTR render_kernel(const KAr
   // LDS, structure-of-arrays so every access is bank-conflict-free; keystream blocks in the slab.
   __shared__ double c_sum[3 * BLOCK];
   __shared__ double c_T[3 * BLOCK];
-  // (8 words per lane: one more would push the block past 40 KB of LDS and cost a block per CU)
+  // (8 words per lane, 80 B of cold state with the two arrays above: a one-wave block may hold 10 KB of LDS at 16
+  // blocks per CU, and every word here is one the traversal stack does not get)
   __shared__ uint32_t c_u[8 * BLOCK];
   const uint32_t tid = threadIdx.x;
   uint32_t& slot = c_u[tid];

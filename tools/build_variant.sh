@@ -18,9 +18,9 @@ TMP=$(mktemp -d)
 trap 'rm -rf "$TMP"' EXIT
 cp "$HERE"/csrc/*.h "$HERE"/csrc/rp_kernel.hip "$TMP"/
 if [ ${#SEDS[@]} -gt 0 ]; then
-  sed -i "${SEDS[@]}" "$TMP/rp_device.h" "$TMP/rp_draw.h" "$TMP/rp_kernel.hip"
+  sed -i "${SEDS[@]}" "$TMP/rp_device.h" "$TMP/rp_draw.h" "$TMP/rp_ray.h" "$TMP/rp_kernel.hip"
   if diff -q "$HERE/csrc/rp_device.h" "$TMP/rp_device.h" >/dev/null && diff -q "$HERE/csrc/rp_draw.h" "$TMP/rp_draw.h" >/dev/null &&
-     diff -q "$HERE/csrc/rp_kernel.hip" "$TMP/rp_kernel.hip" >/dev/null; then
+     diff -q "$HERE/csrc/rp_ray.h" "$TMP/rp_ray.h" >/dev/null && diff -q "$HERE/csrc/rp_kernel.hip" "$TMP/rp_kernel.hip" >/dev/null; then
     echo "build_variant: the expressions changed nothing" >&2; exit 1
   fi
 fi
