@@ -645,7 +645,6 @@ RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, 
     const V3 pa = sub(a, o);
     const double det = ba.x * ca.y * d.z + ba.y * ca.z * d.x + ba.z * ca.x * d.y
                      - ba.x * ca.z * d.y - ba.y * ca.x * d.z - ba.z * ca.y * d.x;
-    if (fabs(det) < SMOL) return;
     const double inv_det = 1.0 / det;
     const double t = (pa.x * (ba.y * ca.z - ba.z * ca.y)
                     + pa.y * (ba.z * ca.x - ba.x * ca.z)
@@ -657,10 +656,21 @@ RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, 
                     + pa.y * (ba.x * d.z - ba.z * d.x)
                     + pa.z * (ba.y * d.x - ba.x * d.y)) * inv_det;
     const double w = 1.0 - u - v;
-    if (t < tmin || t > best || u < 0.0 || v < 0.0 || w < 0.0) return;
-    best = t; ts.bestp = (int32_t)k; ts.bu = u; ts.bv = v; ts.bestm = KM_TRIANGLE | mat;
+    // hittable.rs:75, 97: the reference's six rejections as one predicate (the same comparisons, so the same NaN
+    // behaviour; a |det| below SMOL rejects whatever its inv_det gave) and one masked block that takes the hit.  Early
+    // returns made five nested exec-mask regions, each copying the hit record in and out, around skip branches a wave
+    // with a dozen lanes never takes; five selects instead of the block measured 0.45 % slower on C3
+    // (profiles/r9/c3_leaf_loop_ab.json).
+    const bool rej = (fabs(det) < SMOL) | (t < tmin) | (t > best) | (u < 0.0) | (v < 0.0) | (w < 0.0);
+    if (!rej) {
+      best = t; ts.bestp = (int32_t)k; ts.bu = u; ts.bv = v; ts.bestm = KM_TRIANGLE | mat;
+    }
   } else {
     // hittable.rs:39-57
+    // (the words only the triangle reads count as read here too: all five loads of a test are then issued together in
+    // front of the branch on the kind; with the triangle their only reader the compiler moves their loads into its
+    // path, behind the wait for the kind, and a test waits for memory twice)
+    asm volatile("" : : "v"(g45.x), "v"(g45.y), "v"(g67.x), "v"(g67.y), "v"(g8k.x));
     const V3 c = v3(g01.x, g01.y, g23.x);
     const double radius = g23.y;
     const V3 tc = sub(o, c);
@@ -668,14 +678,18 @@ RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, 
     const double half_b = dot(d, tc);
     const double cq = norm2(tc) - radius * radius;
     const double delta = half_b * half_b - a * cq;
-    if (delta <= 0.0) return;
+    // one predicate and one place that takes the hit, as for the triangle; the second root stays under its branch
+    // (a division that whole waves skip)
+    bool rej = delta <= 0.0;
     const double sq = sqrt(delta);
     double t = (-half_b - sq) / a;
-    if (t < tmin || t > best) {
+    if (!rej && ((t < tmin) | (t > best))) {
       t = (-half_b + sq) / a;
-      if (t < tmin || t > best) return;
+      rej = (t < tmin) | (t > best);
     }
-    best = t; ts.bestp = (int32_t)k; ts.bestm = mat;
+    if (!rej) {
+      best = t; ts.bestp = (int32_t)k; ts.bestm = mat;
+    }
   }
 }
 
@@ -829,18 +843,23 @@ RPK_INLINE void trav_step_w8(const KScene& S, lds_u32* stk, uint32_t stride, uin
     if (!COUNT && (uint32_t)__popcll(__ballot(py == 0u)) <= S.leaf_break) break;
   }
   // ---- leaves: one primitive per lane per iteration from the parked group, then a waiting one
-  while (py != 0u) {
-    DIAG(if (td) td->tests++;)
-    if constexpr (COUNT) *work += WORK_TEST;
-    DREG(DREG_PRIM)
-    const uint32_t k = px + (uint32_t)__builtin_ctz(py);
-    py &= py - 1u;
-    prim_test(S, k, o, d, tmin, best, ts);
-    if (py == 0u) {
-      px = 0u;
-      if (!(gx & W8_GROUP)) w8_settle<SPILL>(S, stk, stride, spl, gx, gy, px, py, sp);  // park the waiting group
+  // (the loop runs on the wave's condition, a lane without a group skips the body: trav_step's leaf loop)
+  uint32_t testing = (uint32_t)__popcll(__ballot(py != 0u));
+  while (testing != 0u) {
+    if (py != 0u) {
+      DIAG(if (td) td->tests++;)
+      if constexpr (COUNT) *work += WORK_TEST;
+      DREG(DREG_PRIM)
+      const uint32_t k = px + (uint32_t)__builtin_ctz(py);
+      py &= py - 1u;
+      prim_test(S, k, o, d, tmin, best, ts);
+      if (py == 0u) {
+        px = 0u;
+        if (!(gx & W8_GROUP)) w8_settle<SPILL>(S, stk, stride, spl, gx, gy, px, py, sp);  // park the waiting group
+      }
     }
-    if (!COUNT && PRIM_BREAK > 0 && (uint32_t)__popcll(__ballot(py != 0u)) <= PRIM_BREAK) break;
+    testing = (uint32_t)__popcll(__ballot(py != 0u));
+    if (!COUNT && PRIM_BREAK > 0 && testing <= PRIM_BREAK) break;
   }
   ts.cur = gx;
   ts.gy = gy;
@@ -1041,22 +1060,30 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
   // lanes with different leaf sizes advance together instead of the wave running every leaf's count.
   uint32_t k = leaf & rpl::LEAF_FIRST_MASK;
   uint32_t kend = k + ((leaf >> rpl::LEAF_SHIFT) & 7u) + 1u;
-  while (leaf != 0u) {
-    DIAG(if (td) td->tests++;)
-    if constexpr (COUNT) *work += WORK_TEST;
-    DREG(DREG_PRIM)
-    prim_test(S, k, o, d, tmin, best, ts);
-    if (++k == kend) {
-      if (cur != rpl::ENTRY_EMPTY && (cur & rpl::ENTRY_LEAF)) {
-        leaf = cur;
-        cur = sp ? pop() : rpl::ENTRY_EMPTY;
-        k = leaf & rpl::LEAF_FIRST_MASK;
-        kend = k + ((leaf >> rpl::LEAF_SHIFT) & 7u) + 1u;
-      } else {
-        leaf = 0u;
+  // The loop runs on the wave's condition (the number of lanes that hold a leaf), a lane without one skips the body:
+  // no lane leaves the loop before the others, so the closest hit, cur and sp stay in one set of registers from the
+  // step's entry to its exit (a per-lane `while (leaf != 0u)` made the compiler keep a copy of all of them for the
+  // lanes that had left, remade at the loop's header and at both ends of the step).
+  uint32_t testing = (uint32_t)__popcll(__ballot(leaf != 0u));
+  while (testing != 0u) {
+    if (leaf != 0u) {
+      DIAG(if (td) td->tests++;)
+      if constexpr (COUNT) *work += WORK_TEST;
+      DREG(DREG_PRIM)
+      prim_test(S, k, o, d, tmin, best, ts);
+      if (++k == kend) {
+        if (cur != rpl::ENTRY_EMPTY && (cur & rpl::ENTRY_LEAF)) {
+          leaf = cur;
+          cur = sp ? pop() : rpl::ENTRY_EMPTY;
+          k = leaf & rpl::LEAF_FIRST_MASK;
+          kend = k + ((leaf >> rpl::LEAF_SHIFT) & 7u) + 1u;
+        } else {
+          leaf = 0u;
+        }
       }
     }
-    if (!COUNT && PRIM_BREAK > 0 && (uint32_t)__popcll(__ballot(leaf != 0u)) <= PRIM_BREAK) {
+    testing = (uint32_t)__popcll(__ballot(leaf != 0u));
+    if (!COUNT && PRIM_BREAK > 0 && testing <= PRIM_BREAK) {
       // park the rest of the current run [k, kend) as a leaf entry; the next step tests it first
       if (leaf != 0u) leaf = rpl::ENTRY_LEAF | ((kend - k - 1u) << rpl::LEAF_SHIFT) | k;
       break;
