@@ -121,6 +121,13 @@ int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_ima
  * nb <= -oinv - D and fb >= -oinv + D; tmin32 <= t_min; best32 >= best (+inf for best = +inf). */
 int rph_ray_setup(uint32_t node_format, double qbound, const double* rays, uint64_t n, float* out);
 
+/* Test hook: the exact f64 primitive tests (raytracing-potato_amd/csrc/rp_isect.h tri_test / sphere_test, the same
+ * header the kernels' prim_test and the CPU traversal model call).  kind: 0 sphere, 1 triangle; g: the nine doubles of
+ * geometry as the packed primitive holds them (triangle: a, a - b, a - c; sphere: centre, radius, the rest unread);
+ * rays: n x 8 {o, d, t_min, best}.  out: n x 4 doubles {accepted (1 or 0), t, u, v}: t, u, v of an accepted test
+ * (a sphere's u and v are 0), zeros for a rejected one.  RP_EINVAL for a NULL pointer or an unknown kind. */
+int rph_prim_test(uint32_t kind, const double g[9], const double* rays, uint64_t n, double* out);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

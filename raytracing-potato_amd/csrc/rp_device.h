@@ -15,6 +15,7 @@
 
 #include "rp_draw.h"
 #include "rp_ray.h"
+#include "rp_isect.h"
 
 // Every compile-time knob below changes timing only.  Experiments that change results (timing ablations
 // with wrong streams or colours) are not kept in this file, and a build asking for one is refused so a
@@ -83,7 +84,16 @@ __shared__ unsigned long long g_dcyc[DCYC_N];
 static constexpr int BLOCK = RENDER_BLOCK;
 typedef float f2 __attribute__((ext_vector_type(2)));
 RPK_INLINE f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-// min(t, best32) for a t that is not NaN (a slab t^: finite, rp_device.h "conservative f32 box test") and
+// The slab test's packed evaluation, two children at a time (v_pk_fma_f32: two fused FMAs with the same per-element
+// rounding as rp_isect.h's plane_t and slab_pass).  q2: code bytes 2h and 2h + 1 of a word (v_cvt_f32_ubyte<b>);
+// pk_pass_lhs: the pass test's left side.
+RPK_INLINE f2 q2(uint32_t w, int h) {
+  return f2{(float)((w >> (16 * h)) & 0xffu), (float)((w >> (16 * h + 8)) & 0xffu)};
+}
+RPK_INLINE f2 pk_pass_lhs(f2 tn) {
+  return pk_fma(tn, f2{rpi::PASS_SCALE, rpi::PASS_SCALE}, f2{rpi::PASS_BIAS, rpi::PASS_BIAS});
+}
+// min(t, best32) for a t that is not NaN (a slab t^: finite, rp_isect.h "conservative f32 box test") and
 // best32 = rpr::best_above(..), whose sign bit is clear: the signed-integer order of the bit patterns is then the
 // floats' order (a negative t is a negative integer, below every best32; two non-negative floats order as their
 // patterns), so v_min_i32 returns the same float as v_min_f32 -- without the v_max_f32 x, x the compiler puts in
@@ -94,7 +104,6 @@ RPK_INLINE float min_best(float t, float best32) {
 }
 static constexpr uint32_t STACK_SLACK = 3;  // spare LDS stack entries for the branchless push (writes reach sp+2 <= cap+2)
 static constexpr double RAY_EPSILON = 1e-3;  // utility.rs:30
-static constexpr double SMOL = 1e-7;         // utility.rs:31
 static constexpr double PI_ = 3.14159265358979323846;
 static constexpr double TAU_ = 6.28318530717958647692;
 static constexpr double INF = __builtin_huge_val();
@@ -457,7 +466,7 @@ RPK_INLINE double gen_f64(RngT<RN>& r) {
 
 // ------------------------------------------------------------------ math -------------------------
 
-struct V3 { double x, y, z; };
+typedef rpi::V3 V3;
 RPK_INLINE V3 v3(double x, double y, double z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
 RPK_INLINE V3 add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 RPK_INLINE V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -510,35 +519,8 @@ struct TravDiag {
   uint32_t visits = 0, tests = 0, trips = 0;
 };
 
-// ---- conservative f32 box test ------------------------------------------------------------------
-//
-// Conservative f32 slab test.  The ray enters in f32 as o32 = fl(o_ray), inv = rcp(fl(d)) (<= 1 ulp),
-// oinv = fl(o32 * inv).  Plane coordinates P are exact: f32 values rounded outward from the exact f64 boxes
-// (Node4), or P = o + q s in a node frame (Node4Q: f32 o and s, 8-bit q, exact in f64).
-//   Node4:  t^ = fma(P, inv, -oinv)
-//   Node4Q: per node and axis A = fl(s inv), B = fma(o, inv, -oinv), and t^ = fma(q, A, B) =
-//           (P inv - oinv)(1 + d3) + e,  |e| <= u (1 + u)(|q s inv| + |o inv - oinv|)
-// The single-rounding form fma(P, inv, -oinv) errs by <= 5u |t| + |o_ray - o32| |inv| (1 + 6u) + u |o32 inv|
-// against the exact t = (P - o_ray) / d (u = 2^-24); with every |o| and |q s| <= qbound (rp_layout.h),
-// |e| <= u (1 + u) |inv| (2 qbound + |o32|) + u^2 |o32 inv|, and e = 0 when inv = +-2^64 (the clamp below)
-// and o32 = 0 (A and B exact).  Call E_a the absolute terms of axis a.  Each axis's planes are moved
-// outward by its own D_a >= E_a, folded into the FMA's addend: near planes use an nb_a <= -oinv_a - D_a, far
-// planes an fb_a >= -oinv_a + D_a (Node4Q: B_near = fma(o, inv, nb_a), B_far = fma(o, inv, fb_a), whose
-// roundings the frame term covers), and the ray's interval enters as tmin32 <= t_min and best32 >= best.  These five
-// inequalities are all the argument uses; rp_ray.h makes the values and shows they hold: D_a in f64, the addends and
-// tmin32 by rounding to nearest and one unconditional step outward (at most one float wider than the exact directed
-// rounding, a third of its instructions), best32 by a three-instruction form that keeps +inf.  A wider addend only
-// passes more boxes.  A box whose exact interval meets [t_min, best] at some t* > 0 then has
-// every near plane <= t*(1 + 6u) (those behind the origin or below tmin32 <= t* do not raise t_near) and
-// every far plane >= t*(1 - 6u), so the test
-//     fma(tnear^, 1 - 2^-19, -2^-100) <= tfar^
-// passes it (2^-19 = 32u).  It may pass a few more boxes, never fewer: no primitive the reference's f64 test
-// reaches is culled.  The error bound is per axis: a ray nearly parallel to an axis has a huge D on that
-// axis only (|inv| is huge there), which widens that slab alone -- with one scalar slack (max over the
-// axes, round 1) such a ray passed every box near the plane it runs in, up to 43 k node visits on C5.
-// Empty slots fail (Node4: lo = +inf, hi = -inf gives t_near = +inf; Node4Q: masked by their entry).  Slopes
-// are clamped to |inv| <= 2^64 (axis-parallel rays) and frames to |o|, 255 s <= 2^56 (rp_layout.h
-// COORD_MAX), so every A, B and t^ is finite; an A that underflows errs by < 2^-118, inside the 2^-100 term.
+// ---- conservative f32 box test: the test and the argument that it never culls a reachable box are rp_isect.h's
+// ("conservative f32 box test"); rp_ray.h makes the ray's side of it.
 struct Ray32 {
   float ix, iy, iz;     // rcp(fl(d))
   float nbx, nby, nbz;  // near-plane addends <= -oinv - D per axis (rp_ray.h)
@@ -549,6 +531,20 @@ struct Ray32 {
                         // the near plane codes out of the {hi, lo} word pair (the far codes out of {lo, hi})
   uint32_t oct;         // Node8Q: dir_octant(d), the children's rank order slot ^ oct
 };
+
+// A node frame's terms for the ray (frame origin c0.xyz, steps c0.w, sy, sz), each in both halves of a pair for the
+// packed plane evaluation.  All A before the B: the instruction order of the node visit is part of its timing.
+struct PkFrame {
+  f2 ax, ay, az, bnx, bny, bnz, bfx, bfy, bfz;
+};
+RPK_INLINE PkFrame pk_frame(float4 c0, float sy, float sz, const Ray32& r) {
+  const float Ax = rpi::frame_a(c0.w, r.ix), Ay = rpi::frame_a(sy, r.iy), Az = rpi::frame_a(sz, r.iz);
+  const float Bnx = rpi::frame_b(c0.x, r.ix, r.nbx), Bny = rpi::frame_b(c0.y, r.iy, r.nby),
+              Bnz = rpi::frame_b(c0.z, r.iz, r.nbz);
+  const float Bfx = rpi::frame_b(c0.x, r.ix, r.fbx), Bfy = rpi::frame_b(c0.y, r.iy, r.fby),
+              Bfz = rpi::frame_b(c0.z, r.iz, r.fbz);
+  return {{Ax, Ax}, {Ay, Ay}, {Az, Az}, {Bnx, Bnx}, {Bny, Bny}, {Bnz, Bnz}, {Bfx, Bfx}, {Bfy, Bfy}, {Bfz, Bfz}};
+}
 
 // Octant of a direction: bit a set when d_a has its sign bit set (the sign of rcp(fl(d_a)) below).  Node8Q
 // visits a node's children in rank order slot ^ octant (rp_layout.h); only the order depends on it.
@@ -627,7 +623,7 @@ RPK_INLINE void trav_init(const KScene& S, double tmax, TravState& t, V3 d) {
   }
 }
 
-// One exact f64 primitive test (the reference's Hittable::hit for a leaf, hittable.rs:39-101): on
+// One exact f64 primitive test (rp_isect.h: the reference's Hittable::hit for a leaf, hittable.rs:39-101): on
 // acceptance `best` shrinks to t and the hit record is taken.
 RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, double& best, TravState& ts) {
   // 32-bit byte offset from the wave-uniform base (scalar-base + vector-offset loads)
@@ -637,59 +633,23 @@ RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, 
   const double2 g8k = q[4];  // g[8], {kind, material}
   const uint64_t km = (uint64_t)__double_as_longlong(g8k.y);
   const uint32_t kind = (uint32_t)km, mat = (uint32_t)(km >> 32);
+  const V3 g0 = v3(g01.x, g01.y, g23.x);  // the triangle's a, the sphere's centre
   if (kind == rpl::PRIM_TRIANGLE) {
-    // hittable.rs:65-101, exact expression order; ba, ca were pre-subtracted (same IEEE op)
-    const V3 a = v3(g01.x, g01.y, g23.x);
-    const V3 ba = v3(g23.y, g45.x, g45.y);
-    const V3 ca = v3(g67.x, g67.y, g8k.x);
-    const V3 pa = sub(a, o);
-    const double det = ba.x * ca.y * d.z + ba.y * ca.z * d.x + ba.z * ca.x * d.y
-                     - ba.x * ca.z * d.y - ba.y * ca.x * d.z - ba.z * ca.y * d.x;
-    const double inv_det = 1.0 / det;
-    const double t = (pa.x * (ba.y * ca.z - ba.z * ca.y)
-                    + pa.y * (ba.z * ca.x - ba.x * ca.z)
-                    + pa.z * (ba.x * ca.y - ba.y * ca.x)) * inv_det;
-    const double u = (pa.x * (ca.y * d.z - ca.z * d.y)
-                    + pa.y * (ca.z * d.x - ca.x * d.z)
-                    + pa.z * (ca.x * d.y - ca.y * d.x)) * inv_det;
-    const double v = (pa.x * (ba.z * d.y - ba.y * d.z)
-                    + pa.y * (ba.x * d.z - ba.z * d.x)
-                    + pa.z * (ba.y * d.x - ba.x * d.y)) * inv_det;
-    const double w = 1.0 - u - v;
-    // hittable.rs:75, 97: the reference's six rejections as one predicate (the same comparisons, so the same NaN
-    // behaviour; a |det| below SMOL rejects whatever its inv_det gave) and one masked block that takes the hit.  Early
-    // returns made five nested exec-mask regions, each copying the hit record in and out, around skip branches a wave
-    // with a dozen lanes never takes; five selects instead of the block measured 0.45 % slower on C3
-    // (profiles/r9/c3_leaf_loop_ab.json).
-    const bool rej = (fabs(det) < SMOL) | (t < tmin) | (t > best) | (u < 0.0) | (v < 0.0) | (w < 0.0);
-    if (!rej) {
+    // One masked block takes the hit.  Early returns made five nested exec-mask regions, each copying the hit record
+    // in and out, around skip branches a wave with a dozen lanes never takes; five selects instead of the block
+    // measured 0.45 % slower on C3 (profiles/r9/c3_leaf_loop_ab.json).
+    const V3 ba = v3(g23.y, g45.x, g45.y), ca = v3(g67.x, g67.y, g8k.x);
+    rpi::tri_test(g0, ba, ca, o, d, tmin, best, [&](double t, double u, double v) {
       best = t; ts.bestp = (int32_t)k; ts.bu = u; ts.bv = v; ts.bestm = KM_TRIANGLE | mat;
-    }
+    });
   } else {
-    // hittable.rs:39-57
     // (the words only the triangle reads count as read here too: all five loads of a test are then issued together in
     // front of the branch on the kind; with the triangle their only reader the compiler moves their loads into its
     // path, behind the wait for the kind, and a test waits for memory twice)
     asm volatile("" : : "v"(g45.x), "v"(g45.y), "v"(g67.x), "v"(g67.y), "v"(g8k.x));
-    const V3 c = v3(g01.x, g01.y, g23.x);
-    const double radius = g23.y;
-    const V3 tc = sub(o, c);
-    const double a = norm2(d);
-    const double half_b = dot(d, tc);
-    const double cq = norm2(tc) - radius * radius;
-    const double delta = half_b * half_b - a * cq;
-    // one predicate and one place that takes the hit, as for the triangle; the second root stays under its branch
-    // (a division that whole waves skip)
-    bool rej = delta <= 0.0;
-    const double sq = sqrt(delta);
-    double t = (-half_b - sq) / a;
-    if (!rej && ((t < tmin) | (t > best))) {
-      t = (-half_b + sq) / a;
-      rej = (t < tmin) | (t > best);
-    }
-    if (!rej) {
+    rpi::sphere_test(g0, g23.y, o, d, tmin, best, [&](double t) {
       best = t; ts.bestp = (int32_t)k; ts.bestm = mat;
-    }
+    });
   }
 }
 
@@ -788,13 +748,8 @@ RPK_INLINE void trav_step_w8(const KScene& S, lds_u32* stk, uint32_t stride, uin
     const uint4 cz = *reinterpret_cast<const uint4*>(nb + (no + 64u));
     const uint4 pa = *reinterpret_cast<const uint4*>(nb + (no + 80u));  // pmask[0-3]
     const uint4 pb = *reinterpret_cast<const uint4*>(nb + (no + 96u));  // pmask[4-7]
-    const float Ax = c0.w * r.ix, Ay = __uint_as_float(c1.x) * r.iy, Az = __uint_as_float(c1.y) * r.iz;
-    const float Bnx = fmaf(c0.x, r.ix, r.nbx), Bny = fmaf(c0.y, r.iy, r.nby), Bnz = fmaf(c0.z, r.iz, r.nbz);
-    const float Bfx = fmaf(c0.x, r.ix, r.fbx), Bfy = fmaf(c0.y, r.iy, r.fby), Bfz = fmaf(c0.z, r.iz, r.fbz);
-    const f2 ax = {Ax, Ax}, ay = {Ay, Ay}, az = {Az, Az};
-    const f2 bnx = {Bnx, Bnx}, bny = {Bny, Bny}, bnz = {Bnz, Bnz}, bfx = {Bfx, Bfx}, bfy = {Bfy, Bfy}, bfz = {Bfz, Bfz};
+    const PkFrame f = pk_frame(c0, __uint_as_float(c1.x), __uint_as_float(c1.y), r);
     uint32_t hits = 0u, pm = 0u;
-#define RPK_Q2(w, h) f2{(float)(((w) >> (16 * (h))) & 0xffu), (float)(((w) >> (16 * (h) + 8)) & 0xffu)}
 #pragma unroll
     for (int half = 0; half < 2; half++) {  // children 4 half .. 4 half + 3
       const uint32_t lx = half ? cx.y : cx.x, hx = half ? cx.w : cx.z;
@@ -806,16 +761,16 @@ RPK_INLINE void trav_step_w8(const KScene& S, lds_u32* stk, uint32_t stride, uin
       const uint4 pq = half ? pb : pa;
 #pragma unroll
       for (int q = 0; q < 2; q++) {
-        const f2 NX = pk_fma(RPK_Q2(qnx, q), ax, bnx), FX = pk_fma(RPK_Q2(qfx, q), ax, bfx);
-        const f2 NY = pk_fma(RPK_Q2(qny, q), ay, bny), FY = pk_fma(RPK_Q2(qfy, q), ay, bfy);
-        const f2 NZ = pk_fma(RPK_Q2(qnz, q), az, bnz), FZ = pk_fma(RPK_Q2(qfz, q), az, bfz);
+        const f2 NX = pk_fma(q2(qnx, q), f.ax, f.bnx), FX = pk_fma(q2(qfx, q), f.ax, f.bfx);
+        const f2 NY = pk_fma(q2(qny, q), f.ay, f.bny), FY = pk_fma(q2(qfy, q), f.ay, f.bfy);
+        const f2 NZ = pk_fma(q2(qnz, q), f.az, f.bnz), FZ = pk_fma(q2(qfz, q), f.az, f.bfz);
         f2 TN, TF;
 #pragma unroll
         for (int e = 0; e < 2; e++) {
           TN[e] = fmaxf(fmaxf(NX[e], NY[e]), fmaxf(NZ[e], r.tmin));
           TF[e] = min_best(fminf(fminf(FX[e], FY[e]), FZ[e]), best32);
         }
-        const f2 lhs = pk_fma(TN, f2{1.0f - 0x1p-19f, 1.0f - 0x1p-19f}, f2{-0x1p-100f, -0x1p-100f});
+        const f2 lhs = pk_pass_lhs(TN);
 #pragma unroll
         for (int e = 0; e < 2; e++) {
           const int c = 4 * half + 2 * q + e;
@@ -826,7 +781,6 @@ RPK_INLINE void trav_step_w8(const KScene& S, lds_u32* stk, uint32_t stride, uin
         }
       }
     }
-#undef RPK_Q2
     // hit inner children in rank order: bit (slot ^ oct)
     const uint32_t imask = c1.z >> 24;
     uint32_t ih = hits & imask;
@@ -902,28 +856,20 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
       const uint4 c1 = *reinterpret_cast<const uint4*>(nb + (no + 16u));  // s.y s.z lo_x hi_x
       const uint4 c2 = *reinterpret_cast<const uint4*>(nb + (no + 32u));  // lo_y hi_y lo_z hi_z
       ch = *reinterpret_cast<const uint4*>(nb + (no + 48u));
-      // per axis: A = s inv, B = fma(o, inv, -oinv); plane t^ = fma(q, A, B)
-      const float Ax = c0.w * r.ix, Ay = __uint_as_float(c1.x) * r.iy, Az = __uint_as_float(c1.y) * r.iz;
-      const float Bnx = fmaf(c0.x, r.ix, r.nbx), Bny = fmaf(c0.y, r.iy, r.nby), Bnz = fmaf(c0.z, r.iz, r.nbz);
-      const float Bfx = fmaf(c0.x, r.ix, r.fbx), Bfy = fmaf(c0.y, r.iy, r.fby), Bfz = fmaf(c0.z, r.iz, r.fbz);
+      // per axis: A = s inv, B = fma(o, inv, nb | fb); plane t^ = fma(q, A, B)
+      const PkFrame f = pk_frame(c0, __uint_as_float(c1.x), __uint_as_float(c1.y), r);
       const uint32_t qnx = __builtin_amdgcn_perm(c1.w, c1.z, r.sx), qfx = __builtin_amdgcn_perm(c1.z, c1.w, r.sx);
       const uint32_t qny = __builtin_amdgcn_perm(c2.y, c2.x, r.sy), qfy = __builtin_amdgcn_perm(c2.x, c2.y, r.sy);
       const uint32_t qnz = __builtin_amdgcn_perm(c2.w, c2.z, r.sz), qfz = __builtin_amdgcn_perm(c2.z, c2.w, r.sz);
-      // children (0,1) and (2,3) as packed pairs: v_pk_fma_f32 is two fused FMAs with the same per-element
-      // rounding as fmaf; byte b of a code word converts with v_cvt_f32_ubyte<b>
-      const f2 ax = {Ax, Ax}, ay = {Ay, Ay}, az = {Az, Az};
-      const f2 bnx = {Bnx, Bnx}, bny = {Bny, Bny}, bnz = {Bnz, Bnz}, bfx = {Bfx, Bfx}, bfy = {Bfy, Bfy}, bfz = {Bfz, Bfz};
-#define RPK_Q2(w, h) f2{(float)(((w) >> (16 * (h))) & 0xffu), (float)(((w) >> (16 * (h) + 8)) & 0xffu)}
-#pragma unroll
+#pragma unroll  // children (0,1) and (2,3) as packed pairs
       for (int q = 0; q < 2; q++) {
-        NX[q] = pk_fma(RPK_Q2(qnx, q), ax, bnx);
-        FX[q] = pk_fma(RPK_Q2(qfx, q), ax, bfx);
-        NY[q] = pk_fma(RPK_Q2(qny, q), ay, bny);
-        FY[q] = pk_fma(RPK_Q2(qfy, q), ay, bfy);
-        NZ[q] = pk_fma(RPK_Q2(qnz, q), az, bnz);
-        FZ[q] = pk_fma(RPK_Q2(qfz, q), az, bfz);
+        NX[q] = pk_fma(q2(qnx, q), f.ax, f.bnx);
+        FX[q] = pk_fma(q2(qfx, q), f.ax, f.bfx);
+        NY[q] = pk_fma(q2(qny, q), f.ay, f.bny);
+        FY[q] = pk_fma(q2(qfy, q), f.ay, f.bfy);
+        NZ[q] = pk_fma(q2(qnz, q), f.az, f.bnz);
+        FZ[q] = pk_fma(q2(qfz, q), f.az, f.bfz);
       }
-#undef RPK_Q2
     } else {
       const uint32_t no = cur << 7;
       const float4 nx = *reinterpret_cast<const float4*>(nb + (no + r.sx));
@@ -955,7 +901,7 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
         TF[q][e] = min_best(fminf(fminf(FX[q][e], FY[q][e]), FZ[q][e]), best32);
       }
       // fma(tnear, 1 - 2^-19, -2^-100) <= tfar (section 4.2 of DESIGN.md): one packed FMA per pair
-      const f2 lhs = pk_fma(TN[q], f2{1.0f - 0x1p-19f, 1.0f - 0x1p-19f}, f2{-0x1p-100f, -0x1p-100f});
+      const f2 lhs = pk_pass_lhs(TN[q]);
 #pragma unroll
       for (int e = 0; e < 2; e++) {
         const int c = 2 * q + e;

@@ -14,6 +14,7 @@
 
 #include "rp_bvh.h"
 #include "rp_draw.h"
+#include "rp_isect.h"
 #include "rp_kernel.h"
 #include "rp_ray.h"
 #include "rp_schedule.h"
@@ -156,6 +157,50 @@ uint8_t quant(double x) {
   if (!(x > 0.0)) return 0;
   if (x >= 1.0) return 255;
   return (uint8_t)(x * 255.0 + 0.5);
+}
+
+// The slab test's terms over one node, per axis: the plane slope and the near and far addends -- the ray's own
+// {inv, nb, fb} (rp_ray.h) for f32 planes, a frame's {A, Bn, Bf} (rp_isect.h frame_axis) for 8-bit codes.
+struct Slabs {
+  float A[3], Bn[3], Bf[3];
+};
+template <class Node>
+Slabs frame_slabs(const Node& nd, const Slabs& ray) {
+  Slabs f;
+  for (int k = 0; k < 3; k++) {
+    const rpi::FrameAxis a = rpi::frame_axis(nd.o[k], nd.s[k], ray.A[k], ray.Bn[k], ray.Bf[k]);
+    f.A[k] = a.A;
+    f.Bn[k] = a.Bn;
+    f.Bf[k] = a.Bf;
+  }
+  return f;
+}
+// The children of a node (Node4: f32 planes; Node4Q, Node8Q: codes) that pass the slab test, as a bit mask, and every
+// child's tnear.  Both planes with each addend and min / max where the kernel picks the near and the far plane by the
+// slope's sign: the same pair of values.
+template <class Node>
+uint32_t children_hit(const Node& nd, const Slabs& s, float tmin32, float best32, float* tn) {
+  const decltype(&nd.lo_x[0]) lo[3] = {nd.lo_x, nd.lo_y, nd.lo_z}, hi[3] = {nd.hi_x, nd.hi_y, nd.hi_z};
+  uint32_t hits = 0;
+  for (int c = 0; c < (int)(sizeof nd.lo_x / sizeof nd.lo_x[0]); c++) {
+    float tnear = tmin32, tfar = best32;
+    for (int k = 0; k < 3; k++) {
+      const float l = (float)lo[k][c], h = (float)hi[k][c];
+      tnear = fmaxf(tnear, fminf(rpi::plane_t(l, s.A[k], s.Bn[k]), rpi::plane_t(h, s.A[k], s.Bn[k])));
+      tfar = fminf(tfar, fmaxf(rpi::plane_t(l, s.A[k], s.Bf[k]), rpi::plane_t(h, s.A[k], s.Bf[k])));
+    }
+    tn[c] = tnear;
+    if (rpi::slab_pass(tnear, tfar)) hits |= 1u << c;
+  }
+  return hits;
+}
+
+// One exact test of a primitive with geometry g (rpl::Prim::g); accepted: take(t, u, v) (a sphere: u = v = 0).
+template <class Take>
+void prim_test(uint32_t kind, const double* g, rpi::V3 o, rpi::V3 d, double tmin, double best, Take take) {
+  const rpi::V3 g0 = {g[0], g[1], g[2]};
+  if (kind == rpl::PRIM_TRIANGLE) rpi::tri_test(g0, {g[3], g[4], g[5]}, {g[6], g[7], g[8]}, o, d, tmin, best, take);
+  else rpi::sphere_test(g0, g[3], o, d, tmin, best, [&](double t) { take(t, 0.0, 0.0); });
 }
 
 }  // namespace
@@ -422,12 +467,12 @@ int rph_bvh_traversal_stats(const rp_scene_desc* desc, const double* rays, uint6
 
 int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, uint64_t n, uint32_t node_format,
                                uint32_t collapse, uint64_t* per_ray) {
-  // CPU model of rp_device.h's traversal over the same packed 4-wide tree: child boxes tested in f32 with
-  // per-axis outward bounds (t = fma(P, inv, nb|fb), quantized: fma(q, s inv, fma(o, inv, nb|fb))), rcp
-  // emulated by a correctly rounded 1/x, the min/max slab form instead of the device's octant selection
-  // (the same values), near-first order, exact f64
-  // primitive tests.  per_ray: n x 3 {wide nodes visited, primitive tests, closest hittable id or
-  // 2^64-1}.  tests/test_bvh.py checks the closest hits against brute force.
+  // CPU model of rp_device.h's traversal over the same packed tree.  The arithmetic is the kernel's source: the ray
+  // setup (rp_ray.h), the frame terms, plane t^ and pass test of the conservative f32 slab test and the exact f64
+  // primitive tests (rp_isect.h) -- except the reciprocal, a correctly rounded 1/x for the device's v_rcp_f32.  The
+  // model's own: the min/max slab form instead of the device's octant selection (the same values), one child at a
+  // time, near-first order, leaf primitives tested when reached.  per_ray: n x 3 {wide nodes visited, primitive
+  // tests, closest hittable id or 2^64-1}.  tests/test_bvh.py checks the closest hits against brute force.
   std::string err;
   int rc = rpb::validate(desc, err);
   if (rc != RP_OK) return fail(err);
@@ -441,14 +486,15 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
   const bool w8 = ps.node_format == rpl::NODES_W8;
   for (uint64_t r = 0; r < n; r++) {
     const double* q = rays + 8 * r;
-    const double o[3] = {q[0], q[1], q[2]}, d[3] = {q[3], q[4], q[5]};
+    const rpi::V3 o = {q[0], q[1], q[2]}, d = {q[3], q[4], q[5]};
     const double tmin = q[6];
-    float inv[3], nb[3], fb[3];  // per axis: slope, near- and far-plane addends (rp_ray.h, as rp_device.h setup_ray32)
+    Slabs ray;  // per axis: slope, near- and far-plane addends (rp_ray.h, as rp_device.h setup_ray32)
     for (int k = 0; k < 3; k++) {
-      const rpr::Axis a = q8 ? rpr::axis_setup<true>(o[k], d[k], ps.qbound) : rpr::axis_setup<false>(o[k], d[k], 0.0);
-      inv[k] = a.inv;
-      nb[k] = a.nb;
-      fb[k] = a.fb;
+      const rpr::Axis a =
+          q8 ? rpr::axis_setup<true>(q[k], q[3 + k], ps.qbound) : rpr::axis_setup<false>(q[k], q[3 + k], 0.0);
+      ray.A[k] = a.inv;
+      ray.Bn[k] = a.nb;
+      ray.Bf[k] = a.fb;
     }
     const float tmin32 = rpr::f32_below(tmin);
     double best = q[7];
@@ -457,72 +503,24 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
     uint64_t visits = 0, tests = 0;
     auto test = [&](uint32_t k) {
       tests++;
-      const rpl::Prim& p = ps.prims[k];
-      if (p.kind == rpl::PRIM_TRIANGLE) {
-        const double* g = p.g;
-        const double pa[3] = {g[0] - o[0], g[1] - o[1], g[2] - o[2]};
-        const double ba[3] = {g[3], g[4], g[5]}, ca[3] = {g[6], g[7], g[8]};
-        double det = ba[0] * ca[1] * d[2] + ba[1] * ca[2] * d[0] + ba[2] * ca[0] * d[1] - ba[0] * ca[2] * d[1] -
-                     ba[1] * ca[0] * d[2] - ba[2] * ca[1] * d[0];
-        if (std::fabs(det) < 1e-7) return;
-        double inv_det = 1.0 / det;
-        double t = (pa[0] * (ba[1] * ca[2] - ba[2] * ca[1]) + pa[1] * (ba[2] * ca[0] - ba[0] * ca[2]) +
-                    pa[2] * (ba[0] * ca[1] - ba[1] * ca[0])) * inv_det;
-        double u = (pa[0] * (ca[1] * d[2] - ca[2] * d[1]) + pa[1] * (ca[2] * d[0] - ca[0] * d[2]) +
-                    pa[2] * (ca[0] * d[1] - ca[1] * d[0])) * inv_det;
-        double v = (pa[0] * (ba[2] * d[1] - ba[1] * d[2]) + pa[1] * (ba[0] * d[2] - ba[2] * d[0]) +
-                    pa[2] * (ba[1] * d[0] - ba[0] * d[1])) * inv_det;
-        double w = 1.0 - u - v;
-        if (t < tmin || t > best || u < 0.0 || v < 0.0 || w < 0.0) return;
+      prim_test(ps.prims[k].kind, ps.prims[k].g, o, d, tmin, best, [&](double t, double, double) {
         best = t;
         bestp = ps.prim_refs[k].src;
-      } else {
-        const double tc[3] = {o[0] - p.g[0], o[1] - p.g[1], o[2] - p.g[2]};
-        double a = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-        double hb = (d[0] * tc[0] + d[1] * tc[1]) + d[2] * tc[2];
-        double cq = ((tc[0] * tc[0] + tc[1] * tc[1]) + tc[2] * tc[2]) - p.g[3] * p.g[3];
-        double delta = hb * hb - a * cq;
-        if (delta <= 0.0) return;
-        double sq = std::sqrt(delta);
-        double t = (-hb - sq) / a;
-        if (t < tmin || t > best) {
-          t = (-hb + sq) / a;
-          if (t < tmin || t > best) return;
-        }
-        best = t;
-        bestp = ps.prim_refs[k].src;
-      }
-      best32 = rpr::best_above(best);
+        best32 = rpr::best_above(best);
+      });
     };
     // the always-tested primitives first (rp_bvh.h BuildOptions::always_max), as the kernel does
     for (uint32_t k = ps.always_first; k < ps.always_first + ps.n_always; k++) test(k);
     if (w8) {
       // 8-wide: children in rank order slot ^ octant; a stack of groups {family index | imask, rank bits}; the
       // leaf children's primitives are tested when their node is visited (the kernel parks them, same hits)
-      const uint32_t oct = (d[0] < 0.0 ? 1u : 0u) | (d[1] < 0.0 ? 2u : 0u) | (d[2] < 0.0 ? 4u : 0u);
+      const uint32_t oct = (d.x < 0.0 ? 1u : 0u) | (d.y < 0.0 ? 2u : 0u) | (d.z < 0.0 ? 4u : 0u);
       std::vector<std::pair<uint32_t, uint32_t>> groups;  // {inner word, remaining rank bits}
       auto visit = [&](uint32_t node) {
         visits++;
         const rpl::Node8Q& nd = ps.wnodes[node];
-        float A[3], Bn[3], Bf[3];
-        for (int k = 0; k < 3; k++) {
-          A[k] = nd.s[k] * inv[k];
-          Bn[k] = std::fma(nd.o[k], inv[k], nb[k]);
-          Bf[k] = std::fma(nd.o[k], inv[k], fb[k]);
-        }
-        const uint8_t* L[3] = {nd.lo_x, nd.lo_y, nd.lo_z};
-        const uint8_t* H[3] = {nd.hi_x, nd.hi_y, nd.hi_z};
-        uint32_t hits = 0;
-        for (int c = 0; c < 8; c++) {
-          float tnear = tmin32, tfar = best32;
-          for (int k = 0; k < 3; k++) {
-            const float a = std::fma((float)L[k][c], A[k], Bn[k]), b = std::fma((float)H[k][c], A[k], Bn[k]);
-            const float a2 = std::fma((float)L[k][c], A[k], Bf[k]), b2 = std::fma((float)H[k][c], A[k], Bf[k]);
-            tnear = std::fmax(tnear, std::fmin(a, b));
-            tfar = std::fmin(tfar, std::fmax(a2, b2));
-          }
-          if (std::fma(tnear, 1.0f - 0x1p-19f, -0x1p-100f) <= tfar) hits |= 1u << c;
-        }
+        float tn[8];
+        const uint32_t hits = children_hit(nd, frame_slabs(nd, ray), tmin32, best32, tn);
         uint32_t pm = 0;
         for (int c = 0; c < 8; c++)
           if (hits >> c & 1u) pm |= nd.pmask[c];
@@ -541,76 +539,36 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
         if (!g.second) groups.pop_back();
         visit((word & rpl::W8_INDEX) + (uint32_t)__builtin_popcount((word >> 24) & ((1u << slot) - 1u)));
       }
-      per_ray[3 * r] = visits;
-      per_ray[3 * r + 1] = tests;
-      per_ray[3 * r + 2] = bestp < 0 ? ~0ull : (uint64_t)bestp;
-      continue;
-    }
-    std::vector<uint32_t> stack;
-    uint32_t cur = ps.root;
-    for (;;) {
-      while (!(cur & rpl::ENTRY_LEAF)) {
-        visits++;
-        const uint32_t* child;
-        float near4[4][3], far4[4][3];  // per child and axis: both planes with the near / far addend
-        if (q8) {
-          const rpl::Node4Q& nd = ps.qnodes[cur];
-          float A[3], Bn[3], Bf[3];
-          for (int k = 0; k < 3; k++) {
-            A[k] = nd.s[k] * inv[k];
-            Bn[k] = std::fma(nd.o[k], inv[k], nb[k]);
-            Bf[k] = std::fma(nd.o[k], inv[k], fb[k]);
+    } else {
+      std::vector<uint32_t> stack;
+      uint32_t cur = ps.root;
+      for (;;) {
+        while (!(cur & rpl::ENTRY_LEAF)) {
+          visits++;
+          float tn[4];
+          const uint32_t hits = q8 ? children_hit(ps.qnodes[cur], frame_slabs(ps.qnodes[cur], ray), tmin32, best32, tn)
+                                   : children_hit(ps.nodes[cur], ray, tmin32, best32, tn);
+          const uint32_t* child = q8 ? ps.qnodes[cur].child : ps.nodes[cur].child;
+          uint32_t cc[4];
+          for (int c = 0; c < 4; c++) {
+            if (!(hits >> c & 1u) || child[c] == rpl::ENTRY_EMPTY) tn[c] = INFINITY;
+            cc[c] = child[c];
           }
-          const uint8_t* L[3] = {nd.lo_x, nd.lo_y, nd.lo_z};
-          const uint8_t* H[3] = {nd.hi_x, nd.hi_y, nd.hi_z};
-          // plane t values directly: t = fma(q, A, B) (the device's dequantized form)
-          for (int c = 0; c < 4; c++)
-            for (int k = 0; k < 3; k++) {
-              const float a = std::fma((float)L[k][c], A[k], Bn[k]), b = std::fma((float)H[k][c], A[k], Bn[k]);
-              const float a2 = std::fma((float)L[k][c], A[k], Bf[k]), b2 = std::fma((float)H[k][c], A[k], Bf[k]);
-              near4[c][k] = std::fmin(a, b);
-              far4[c][k] = std::fmax(a2, b2);
-            }
-          child = nd.child;
-        } else {
-          const rpl::Node4& nd = ps.nodes[cur];
-          const float* lo[3] = {nd.lo_x, nd.lo_y, nd.lo_z};
-          const float* hi[3] = {nd.hi_x, nd.hi_y, nd.hi_z};
-          for (int c = 0; c < 4; c++)
-            for (int k = 0; k < 3; k++) {
-              const float a = std::fma(lo[k][c], inv[k], nb[k]), b = std::fma(hi[k][c], inv[k], nb[k]);
-              const float a2 = std::fma(lo[k][c], inv[k], fb[k]), b2 = std::fma(hi[k][c], inv[k], fb[k]);
-              near4[c][k] = std::fmin(a, b);
-              far4[c][k] = std::fmax(a2, b2);
-            }
-          child = nd.child;
+          for (int a = 0; a < 4; a++)  // stable sort by tn (matches the device network for distinct keys)
+            for (int b = a + 1; b < 4; b++)
+              if (tn[b] < tn[a]) { std::swap(tn[a], tn[b]); std::swap(cc[a], cc[b]); }
+          for (int c = 3; c >= 1; c--)
+            if (tn[c] != INFINITY) stack.push_back(cc[c]);
+          if (tn[0] != INFINITY) cur = cc[0];
+          else if (stack.empty()) cur = rpl::ENTRY_EMPTY;
+          else { cur = stack.back(); stack.pop_back(); }
         }
-        float tn[4];
-        uint32_t cc[4];
-        for (int c = 0; c < 4; c++) {
-          float tnear = tmin32, tfar = best32;
-          for (int k = 0; k < 3; k++) {
-            tnear = std::fmax(tnear, near4[c][k]);
-            tfar = std::fmin(tfar, far4[c][k]);
-          }
-          const bool hit = std::fma(tnear, 1.0f - 0x1p-19f, -0x1p-100f) <= tfar && child[c] != rpl::ENTRY_EMPTY;
-          tn[c] = hit ? tnear : INFINITY;
-          cc[c] = child[c];
-        }
-        for (int a = 0; a < 4; a++)  // stable sort by tn (matches the device network for distinct keys)
-          for (int b = a + 1; b < 4; b++)
-            if (tn[b] < tn[a]) { std::swap(tn[a], tn[b]); std::swap(cc[a], cc[b]); }
-        for (int c = 3; c >= 1; c--)
-          if (tn[c] != INFINITY) stack.push_back(cc[c]);
-        if (tn[0] != INFINITY) cur = cc[0];
-        else if (stack.empty()) cur = rpl::ENTRY_EMPTY;
+        if (cur == rpl::ENTRY_EMPTY) break;
+        const uint32_t first = cur & rpl::LEAF_FIRST_MASK, cnt = ((cur >> rpl::LEAF_SHIFT) & 7u) + 1u;
+        for (uint32_t k = first; k < first + cnt; k++) test(k);
+        if (stack.empty()) cur = rpl::ENTRY_EMPTY;
         else { cur = stack.back(); stack.pop_back(); }
       }
-      if (cur == rpl::ENTRY_EMPTY) break;
-      const uint32_t first = cur & rpl::LEAF_FIRST_MASK, cnt = ((cur >> rpl::LEAF_SHIFT) & 7u) + 1u;
-      for (uint32_t k = first; k < first + cnt; k++) test(k);
-      if (stack.empty()) cur = rpl::ENTRY_EMPTY;
-      else { cur = stack.back(); stack.pop_back(); }
     }
     per_ray[3 * r] = visits;
     per_ray[3 * r + 1] = tests;
@@ -749,6 +707,20 @@ int rph_ray_setup(uint32_t node_format, double qbound, const double* rays, uint6
     }
     o[9] = rpr::f32_below(q[6]);
     o[10] = rpr::best_above(q[7]);
+  }
+  return RP_OK;
+}
+
+int rph_prim_test(uint32_t kind, const double g[9], const double* rays, uint64_t n, double* out) {
+  if ((kind != rpl::PRIM_SPHERE && kind != rpl::PRIM_TRIANGLE) || !g || (n && (!rays || !out)))
+    return fail("rph_prim_test: kind 0 (sphere) or 1 (triangle), non-NULL pointers");
+  for (uint64_t r = 0; r < n; r++) {
+    const double* q = rays + 8 * r;
+    double* h = out + 4 * r;
+    h[0] = h[1] = h[2] = h[3] = 0.0;
+    prim_test(kind, g, {q[0], q[1], q[2]}, {q[3], q[4], q[5]}, q[6], q[7], [&](double t, double u, double v) {
+      h[0] = 1.0; h[1] = t; h[2] = u; h[3] = v;
+    });
   }
   return RP_OK;
 }

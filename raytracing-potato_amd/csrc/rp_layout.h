@@ -24,7 +24,7 @@ namespace rpl {
 // one FMA) costs ALU.  Measured: C5 (10 M triangles, SAH tree) -4.4 % frame time,
 // C3 (bunny, L2-resident) +0.7 %.
 //
-// Both are tested with a conservative slab test (rp_device.h trav_step) so no primitive the exact f64
+// Both are tested with a conservative slab test (rp_isect.h, rp_device.h trav_step) so no primitive the exact f64
 // test would accept is ever culled.  Child entries:
 //   inner node : node index (bit 31 clear)
 //   leaf       : ENTRY_LEAF | (count - 1) << LEAF_SHIFT | first primitive   (count 1..8)

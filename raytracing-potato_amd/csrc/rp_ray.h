@@ -1,9 +1,9 @@
 // rp_ray.h -- the arithmetic that takes a ray into the conservative f32 slab test, for host and device.
 //
 // Per axis a the traversal needs the slope inv_a = clamp(rcp(fl(d_a)), +-2^64) and two FMA addends that move the
-// axis's planes outward by D_a >= E_a (the absolute error terms of t^ = fma(P, inv, -oinv), rp_device.h "conservative
+// axis's planes outward by D_a >= E_a (the absolute error terms of t^ = fma(P, inv, -oinv), rp_isect.h "conservative
 // f32 box test" and DESIGN.md 4.2), and per ray tmin32 <= t_min and best32 >= best.  Five inequalities carry the
-// proof that no box the exact f64 test reaches is culled:
+// proof (rp_isect.h: it is written next to the test) that no box the exact f64 test reaches is culled:
 //     nb_a <= -oinv_a - D_a      fb_a >= -oinv_a + D_a      D_a >= E_a      tmin32 <= t_min      best32 >= best
 // with oinv_a = fl(o32_a inv_a), o32_a = fl(o_a) and
 //     E_a = |o_a - o32_a| |inv_a| (1 + 6u) + 2u |o32_a inv_a|                               (u = 2^-24)
@@ -34,9 +34,10 @@
 // +inf -- conservative (boxes are then culled by their slabs alone).  Three instructions.
 //
 // The kernel (rp_device.h setup_ray32, trav_step), the CPU model of the traversal (rp_host.cpp
-// rph_bvh_traversal_stats) and the host test hook (rp_host.h rph_ray_setup) all use this header, so the arithmetic
-// tested on the CPU is the kernel's -- except the reciprocal: the device's v_rcp_f32 (<= 1 ulp) against the host's
-// correctly rounded 1 / x; the proof takes inv as given, whatever its last bit.
+// rph_bvh_traversal_stats) and the host test hook (rp_host.h rph_ray_setup) all use this header, and rp_isect.h for
+// what follows it -- the slab test's frame terms, plane t^ and pass test, and the exact primitive tests -- so the
+// arithmetic tested on the CPU is the kernel's -- except the reciprocal: the device's v_rcp_f32 (<= 1 ulp) against the
+// host's correctly rounded 1 / x; the proof takes inv as given, whatever its last bit.
 #pragma once
 #include <stdint.h>
 

@@ -5,7 +5,7 @@
 //   - the multi-threaded binned-SAH builder and its SAH-optimal / greedy 4-wide collapse at 1, 3, 8 and 16 threads
 //     (rph_bvh_tree_hash: the tree must not depend on the thread count) and the structural self-check, on a random
 //     triangle soup, a mesh with shared vertices and degenerate (zero-area, duplicated) triangles, and spheres;
-//   - the CPU traversal model (rph_bvh_traversal_stats_ex) over random rays;
+//   - the CPU traversal model (rph_bvh_traversal_stats_ex) and the exact primitive tests (rph_prim_test) over random rays;
 //   - the OBJ and TGA readers (mesh.rs:145-183, image.rs:73-114) on files this driver writes, including truncated and
 //     malformed ones (they must fail cleanly), and the TGA writer;
 //   - the bulk StdRng (rph_stdrng_u64, threaded) against the oracle's sequential stream;
@@ -153,6 +153,16 @@ static void check_tree(const char* name, const rp_scene_desc& d) {
   }
   std::vector<uint64_t> per(4 * n);
   for (uint32_t fmt : {1u, 2u, 3u}) CHECK(rph_bvh_traversal_stats_ex(&d, rays.data(), n, fmt, 2u, per.data()) == RP_OK);
+  // the exact primitive tests through their hook: a triangle across the rays' path and a sphere around their origins
+  const double tri[9] = {-4.0, -4.0, 0.0, -16.0, 0.0, 0.0, 0.0, -16.0, 0.0}, sph[9] = {0.0, 0.0, 3.0, 5.0};
+  std::vector<double> hit(4 * n);
+  for (const double* g : {tri, sph}) {
+    CHECK(rph_prim_test(g == tri ? 1u : 0u, g, rays.data(), n, hit.data()) == RP_OK);
+    uint32_t acc = 0;
+    for (uint32_t r = 0; r < n; r++) acc += hit[4 * r] == 1.0;
+    CHECK(acc > n / 2);
+  }
+  CHECK(rph_prim_test(2u, tri, rays.data(), n, hit.data()) == RP_EINVAL);
   std::printf("%s: %u hittables, trees deterministic at 1/3/8/16 threads, self-checks pass\n", name, d.n_hittables);
 }
 
