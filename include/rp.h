@@ -406,6 +406,47 @@ int rp_workspace_unit_order(rp_scene* scene, rp_workspace* workspace, uint32_t* 
 int rp_workspace_tile_map(rp_scene* scene, rp_workspace* workspace, const rp_render_params* params,
                           uint32_t* tile_map, uint32_t n);
 
+/* First-hit feature pass: the noiseless guide buffers a denoiser or compositor takes beside the beauty frame
+ * (render.rs:101 "the first ray of the path tracing provides additional noiseless data like albedo and normal";
+ * PathTraceOutput::normal, render.rs:87-91, zero on a miss at :119).  A pass of its own beside the render, which it
+ * never changes.
+ *   Definition.  The pass traces camera rays only.  Sample k = 0 .. spp-1 of pixel (i, j) is the first camera sample
+ *   of the stream StdRng::seed_from_u64(seed + k*width*height + j*width + i): its uv jitter is the first two draws of a
+ *   clone of that stream (render.rs:74-82), Camera::shoot then draws its UnitDisk from the stream's start
+ *   (render.rs:32-52, drawn even at lens_radius == 0), and root.hit(ray) follows with t_min = 1e-3, t_max = +inf.  That
+ *   is exactly sample 0 of batch k of the RNG contract at samples_per_stream = 1: beside a beauty frame rendered with
+ *   samples_per_stream = 1 the buffers describe the very same camera rays; under any other contract sample 0 is the same
+ *   ray and the rest are fresh camera rays of the same distribution -- what a guide buffer needs.
+ *   params.samples_per_stream and params.max_bounce are ignored.
+ *   Every buffer is (sum over k of [sample k hit ? x_k : 0]) / (double)spp, the sum started at 0.0 and added in k
+ *   order (the batch order of the contract; a miss adds the reference's zero):
+ *     normal (3 f64)  hit.normal as Hittable::hit returns it (a triangle's interpolated normal is not normalised, and
+ *                     never flipped towards the ray);
+ *     albedo (3 f64)  material.absorb.evaluate(ray, hit) (material.rs:74-81: BlackBody, WhiteBody, Albedo, AlbedoMap
+ *                     over every texture kind), evaluated whether or not the material scatters;
+ *     depth  (1 f64)  hit.t;
+ *     fg     (1 f32)  (float)((double)hits / spp), as rp_render's foreground.
+ *   spp = 0: every value is 0 / 0 = NaN, as rp_render's.
+ * rp_render_aov_device_ws: asynchronous on `stream`, never allocates or synchronises (capturable, like
+ * rp_render_device).  Every output is nullable (all four NULL: RP_EINVAL); each is a compact shard buffer in device
+ * memory, rp_shard_pixel_count slots of 3, 3, 1 doubles and 1 float, in the render's shard order (a buffer that is not
+ * asked for costs nothing: without albedo no texture is read).  d_counters (nullable): RP_COUNTERS_LEN uint64, zeroed
+ * on the stream, then {rays = samples = spp x the shard's pixels, pixels, status}.  params.shard, num_shards, tile_w and
+ * tile_h are honoured.  RP_SHARD_INTERLEAVE always works; RP_SHARD_BALANCED uses the plan `workspace` (NULL = the
+ * scene's) holds for this frame shape, so the shard holds the same tiles as the beauty shard rendered before it on that
+ * workspace (the caller orders the two on streams), and without such a plan is RP_EINVAL.  The workspace is read for
+ * nothing else.  spp = 0 or an empty shard launches no kernel and returns RP_OK.
+ * rp_render_aov: the synchronous version into host memory; the buffers are full frames (width*height slots, only the
+ * shard's pixels written, row 0 = bottom), like rp_render's.  stats (nullable): the counters and seconds = device time
+ * of the pass (HIP events).  Any status bit returns RP_EINTERNAL.
+ * Multi-GPU: gathered shards assemble with rp_frame_assemble[_ws] at words_per_slot = 6 (normal, albedo), 2 (depth) or
+ * 1 (fg); on the host rp_shard_unpack[_map] unpacks normal, albedo (channels = 3) and depth (1). */
+int rp_render_aov_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_camera* camera,
+                            const rp_render_params* params, double* d_shard_normal, double* d_shard_albedo,
+                            double* d_shard_depth, float* d_shard_fg, uint64_t* d_counters, void* stream);
+int rp_render_aov(rp_scene* scene, const rp_camera* camera, const rp_render_params* params, double* out_normal,
+                  double* out_albedo, double* out_depth, float* out_fg, rp_stats* stats);
+
 /* Output stage on the device: the reference's to_srgb_u8 (utility.rs:212-220, alpha 255) of every slot of
  * a compact shard buffer, bytes in tga::save's pixel order B, G, R, A (image.rs:116-137), so a gathered
  * and de-interleaved frame is the body of the reference's output.tga (18-byte header: rph_tga_save).

@@ -136,7 +136,8 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_render_multi", "rp_shard_unpack_map", "rp_workspace_tile_map", "rp_frame_assemble_ws", "rp_build_id",
               "rp_workspace_tile_costs", "rp_workspace_set_tile_costs", "rp_scene_build_times",
               "rp_workspace_frame_info", "rp_workspace_reserve_frames", "rp_render_frames_device_ws", "rp_frames_gather",
-              "rp_workspace_unit_order", "rp_frames_block_words", "rp_frames_pack", "rp_frames_unpack"]
+              "rp_workspace_unit_order", "rp_frames_block_words", "rp_frames_pack", "rp_frames_unpack",
+              "rp_render_aov_device_ws", "rp_render_aov"]
 class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
     _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
                 ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
@@ -235,6 +236,10 @@ def rp() -> ctypes.CDLL:
     lib.rp_workspace_set_tile_costs.argtypes = [c_void_p, c_void_p, POINTER(rp_render_params), c_void_p, c_uint32]
     lib.rp_frame_assemble_ws.argtypes = [c_void_p, c_void_p, POINTER(rp_render_params), c_void_p, c_uint32, c_void_p,
                                          c_void_p]
+    lib.rp_render_aov_device_ws.argtypes = [c_void_p, c_void_p, POINTER(rp_camera), POINTER(rp_render_params), c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.rp_render_aov.argtypes = [c_void_p, POINTER(rp_camera), POINTER(rp_render_params), c_void_p, c_void_p, c_void_p,
+                                  c_void_p, POINTER(rp_stats)]
     if lib.rp_abi_version() != RP_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rp_abi_version()}, bindings expect {RP_ABI_VERSION} (rebuild)")
     _rp = lib

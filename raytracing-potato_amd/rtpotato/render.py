@@ -217,6 +217,50 @@ class DeviceScene:
                                                   fg.data_ptr() if fg is not None else None, counters.data_ptr(),
                                                   ctypes.c_void_p(s.cuda_stream)))
 
+    # ---- first-hit feature pass (rp_render_aov*): normal, albedo, depth, foreground ------------------
+    def render_aov(self, params: RenderParams, camera=None, normal: bool = True, albedo: bool = True,
+                   depth: bool = True, foreground: bool = True) -> dict:
+        """rp_render_aov: the guide buffers of the camera rays' first hits, full frames (only the shard's pixels
+        written, others zero): {"normal": (h, w, 3) f64, "albedo": (h, w, 3) f64, "depth": (h, w) f64,
+        "fg": (h, w) f32, "stats": dict}; a buffer that is not asked for is None."""
+        cam = (camera or self.scene.camera).to_c()
+        p = params.to_c()
+        h, w = params.height, params.width
+        out = {"normal": np.zeros((h, w, 3), dtype=np.float64) if normal else None,
+               "albedo": np.zeros((h, w, 3), dtype=np.float64) if albedo else None,
+               "depth": np.zeros((h, w), dtype=np.float64) if depth else None,
+               "fg": np.zeros((h, w), dtype=np.float32) if foreground else None}
+        ptr = {k: (v.ctypes.data if v is not None else None) for k, v in out.items()}
+        st = F.rp_stats()
+        F.check(F.rp().rp_render_aov(self.handle, ctypes.byref(cam), ctypes.byref(p), ptr["normal"], ptr["albedo"],
+                                     ptr["depth"], ptr["fg"], ctypes.byref(st)))
+        out["stats"] = {"rays": st.rays, "samples": st.samples, "pixels": st.pixels, "seconds": st.seconds}
+        return out
+
+    def render_aov_device(self, params: RenderParams, normal=None, albedo=None, depth=None, fg=None, counters=None,
+                          camera=None, stream=None, workspace: "Workspace | None" = None) -> None:
+        """rp_render_aov_device_ws: the shard's guide buffers into torch tensors on `stream` (torch stream; default:
+        current), compact shard order -- normal, albedo: f64, >= 3 * shard_slot_count elements; depth: f64, fg: f32,
+        >= shard_slot_count; counters: int64, RP_COUNTERS_LEN.  Each is optional, at least one output is needed.  A
+        balanced shard (params.shard_map) takes the plan of the beauty render done before on `workspace`."""
+        import torch
+        cam = (camera or self.scene.camera).to_c()
+        p = params.to_c()
+        n = shard_slot_count(params)
+        dev = None
+        for t, dt, m in ((normal, torch.float64, 3 * n), (albedo, torch.float64, 3 * n), (depth, torch.float64, n),
+                         (fg, torch.float32, n), (counters, torch.int64, F.RP_COUNTERS_LEN)):
+            if t is not None:
+                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and t.numel() >= m
+                dev = t.device
+        assert dev is not None, "render_aov_device needs at least one output tensor"
+        if workspace is not None:
+            assert workspace.scene is self and workspace.handle
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        ptr = [t.data_ptr() if t is not None else None for t in (normal, albedo, depth, fg, counters)]
+        F.check(F.rp().rp_render_aov_device_ws(self.handle, workspace.handle if workspace else None, ctypes.byref(cam),
+                                               ctypes.byref(p), *ptr, ctypes.c_void_p(s.cuda_stream)))
+
     def to_bgra8(self, params: RenderParams, shard_rgb, out, stream=None) -> None:
         """Output stage on the device (rp_shard_to_bgra8): the shard's linear f64 RGB (`shard_rgb`, torch
         f64) -> to_srgb_u8 bytes in TGA order B, G, R, A into `out` (torch uint8, >= 4 * slots)."""
