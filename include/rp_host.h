@@ -128,6 +128,35 @@ int rph_ray_setup(uint32_t node_format, double qbound, const double* rays, uint6
  * (a sphere's u and v are 0), zeros for a rejected one.  RP_EINVAL for a NULL pointer or an unknown kind. */
 int rph_prim_test(uint32_t kind, const double g[9], const double* rays, uint64_t n, double* out);
 
+/* Test hook: the render kernel's unit fetch, run on the CPU (raytracing-potato_amd/csrc/rp_units.h fetch_pixel, unit_frame
+ * and unit_spp: the same header the kernel compiles, in a host environment that stands in for the kernarg segment, the
+ * atomics and the wave).  The launch is planned by rps::plan_launch from the arguments rph_plan_launch takes (and must
+ * pass rps::launch_limits with n_blocks lanes); tile_order (n_shard_tiles entries), tile_map (the frame's tiles, a deal
+ * order) and unit_order (n_slots * nbatch entries) are optional (NULL) and set as render_shard's stages set them.
+ * probe_lattice > 0 walks the cost probe of the shard's tiles with that lattice side instead of the render.
+ * queue_groups > 0 replaces the plan's queue count (1 or 8) by another up to 8: the fetch serves any.
+ *
+ * n_blocks blocks of one lane each fetch in rounds -- every block not yet retired fetches once per round, and retires on
+ * its first failed fetch, as a lane does.  units: 8 words per unit in fetch order {slot, pi, pj, global batch, fetching
+ * block, the queue it came from, unit_frame(batch), unit_spp(batch)}, units_cap units of room, *n_units the count.  queue_words and entries:
+ * RPH_QUEUE_WORDS words each -- the final queue words, and per word the fetches that got an entry.
+ *
+ * any_every = n > 0: on every n-th wave vote of the walk, a wave-mate that found the queue drained while this lane did
+ * not is put beside the lane (the vote is forced true).  Such a mate exists only where the lane took its queue's last
+ * entry (the mate's increment, the next of the same wave atomic, is then the first drained one), so the vote is forced
+ * only there; *forced counts the votes that were.
+ *
+ * The environment checks every queue word the fetch touches (a queue below queue_groups, or the probe's word) and every
+ * numerator of a launch-constant division (< 2^31): a violation ends the walk with RP_EINVAL and a message, as do a
+ * refused launch, an order or map entry out of range and more than units_cap units. */
+enum { RPH_QUEUE_WORDS = 288, RPH_UNIT_WORDS = 8 };
+int rph_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w, uint32_t tile_h,
+                  uint32_t shard, uint32_t num_shards, uint32_t samples_per_stream, uint32_t shard_map, uint32_t n_frames,
+                  uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, const uint32_t* tile_order,
+                  const uint32_t* tile_map, const uint32_t* unit_order, uint32_t probe_lattice, uint32_t queue_groups,
+                  uint32_t n_blocks, uint32_t any_every, uint32_t* units, uint64_t units_cap, uint64_t* n_units,
+                  uint32_t* queue_words, uint32_t* entries, uint64_t* forced);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

@@ -26,8 +26,8 @@
 
 namespace rpk {
 
-// The kernarg segment begins with a KArgs, so rp_device.h's kargs() readers (camera_dir, unit_seed, load_scene) find
-// their fields where the render kernel keeps them; the pass's own outputs follow (each nullable).
+// The kernarg segment begins with a KArgs, so the kargs() readers (rp_device.h camera_dir and load_scene, rp_units.h
+// unit_seed) find their fields where the render kernel keeps them; the pass's own outputs follow (each nullable).
 struct AovArgs {
   KArgs k;
   double* normal;  // 3 per slot
@@ -42,13 +42,10 @@ __global__ void __launch_bounds__(BLOCK) aov_kernel(const AovArgs args) {
   KArgsPtr A = kargs();
   const uint64_t slot64 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
   if (slot64 >= A->P.n_slots) return;
-  // slot -> shard tile -> frame tile -> pixel (reduce_batches_kernel's decode); slots of edge tiles outside the frame
-  // are not written
-  const uint32_t slot = (uint32_t)slot64, tw = A->P.tw, th = A->P.th, tile_px = tw * th;
-  const uint32_t k = slot / tile_px, local = slot % tile_px;
-  const uint32_t dk = A->P.shard + k * A->P.nshards, t = A->P.tile_map ? A->P.tile_map[dk] : dk;
-  const uint32_t pi = (t % A->P.tiles_x) * tw + local % tw, pj = (t / A->P.tiles_x) * th + local / tw;
-  if (pi >= A->P.W || pj >= A->P.H) return;
+  // slot -> shard tile -> frame tile -> pixel; slots of edge tiles outside the frame are not written
+  const uint32_t slot = (uint32_t)slot64;
+  uint32_t pi, pj;
+  if (!slot_pixel(A->P, slot, pi, pj)) return;
   const uint32_t spp = A->P.spp;
   unsigned long long* ctr = A->ctr;
   if (ctr) {  // rays = samples = spp x pixels: one atomic per wave and counter

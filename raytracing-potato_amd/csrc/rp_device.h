@@ -16,6 +16,7 @@
 #include "rp_draw.h"
 #include "rp_ray.h"
 #include "rp_isect.h"
+#include "rp_units.h"
 
 // Every compile-time knob below changes timing only.  Experiments that change results (timing ablations
 // with wrong streams or colours) are not kept in this file, and a build asking for one is refused so a
@@ -1377,21 +1378,6 @@ RPK_INLINE V3 matvec(const double* m, V3 v) {  // nalgebra Matrix3 * Vector3 (co
             (v.x * m[2] + v.y * m[5]) + v.z * m[8]);
 }
 
-// All launch arguments in one kernarg struct.  The persistent loop re-reads the fields it needs through
-// a laundered pointer to the kernarg segment (scalar loads, served by the constant cache) instead of
-// keeping ~70 uniform values live in SGPRs for the whole kernel: that SGPR pressure otherwise spills
-// into VGPR lanes and halves the wave occupancy of this register-bound kernel.
-struct KArgs {
-  KScene S;
-  KParams P;
-  double* out;
-  float* out_fg;
-  unsigned long long* ctr;
-  unsigned int* queue;       // the unit queue's next index (workspace-owned, zeroed before the launch)
-  unsigned long long* diag;  // RPK_DIAG builds only (DIAG_N counters)
-};
-typedef const __attribute__((address_space(4))) KArgs* KArgsPtr;
-
 RPK_INLINE KScene load_scene(KArgsPtr A) {
   KScene S;
   S.nodes = A->S.nodes;
@@ -1431,152 +1417,16 @@ RPK_INLINE KArgsPtr kargs() {
   return p;
 }
 
-// Pull the next unit (pixel, sample batch) of the shard from the unit queues.  Queue order: shard tiles
-// (in cost or Z-order when tile_order is set), inside a tile the pixels row-major, each pixel's batches
-// consecutive; slots of edge tiles outside the frame are skipped.  Returns false when every queue is drained.
-RPK_INLINE uint32_t udiv(uint32_t n, uint32_t m, uint32_t s) { return (uint32_t)(((uint64_t)n * m) >> s); }  // rp_kernel.h make_div32
-#define RPK_UDIV(n, dv) udiv((n), A->P.dv.m, A->P.dv.s)
-
-template <bool PROBE>
-RPK_INLINE bool fetch_pixel(uint32_t& slot, uint32_t& pi, uint32_t& pj, uint32_t& batch) {
-  KArgsPtr A = kargs();
-  unsigned int* queue = A->queue;
-  const uint32_t tw = A->P.tw, th = A->P.th;
-  if (PROBE && A->P.probe_n) {  // cost probe: an n x n lattice per tile (cell centres), clamped into the frame
-    slot = atomicAdd(queue, 1u);
-    if ((uint64_t)slot >= A->P.n_queue) return false;
-    batch = 0;
-    const uint32_t n = A->P.probe_n;
-    const uint32_t k = slot / A->P.probe_px, sub = slot % A->P.probe_px;
-    const uint32_t dk = A->P.shard + k * A->P.nshards, t = A->P.tile_map ? A->P.tile_map[dk] : dk;
-    const uint32_t tx = t % A->P.tiles_x, ty = t / A->P.tiles_x;
-    pi = min(tx * tw + min((sub % n) * tw / n + tw / (2u * n), tw - 1u), A->P.W - 1u);
-    pj = min(ty * th + min((sub / n) * th / n + th / (2u * n), th - 1u), A->P.H - 1u);
-    return true;
-  }
-  const uint32_t tile_px = tw * th, tile_units = tile_px * A->P.nbatch;
-  if (!PROBE && A->P.unit_order) {
-    // the learned per-unit order (rp_sched.hip): queue g serves the chunks g, g + G, ... of C consecutive positions,
-    // position p holds unit unit_order[p] = slot * nbatch + batch -- with several frames per launch, position p is frame
-    // p mod n_frames of unit unit_order[p / n_frames] (a unit's frames consecutive); the same drained-queue walk as the
-    // tile queues below
-    const uint32_t G = max(A->P.queue_groups, 1u), C = A->P.order_chunk, GC = G * C;
-    const uint32_t home = G > 1 ? blockIdx.x % G : 0u;
-    const uint32_t Q = (uint32_t)A->P.n_queue;
-    for (uint32_t tries = 0;;) {
-      uint32_t g = home + tries;
-      if (g >= G) g -= G;
-      g = __builtin_amdgcn_readfirstlane(g);
-      const uint32_t rest = Q % GC, nq = (Q / GC) * C + min(rest - min(rest, g * C), C);
-      const uint32_t q = atomicAdd(A->queue + g * QUEUE_STRIDE, 1u);
-      const bool drained = q >= nq;
-      if (__ballot(drained) != 0) {
-        ++tries;
-        if (drained) {
-          if (tries >= G) return false;
-          continue;
-        }
-      }
-      const uint32_t i = RPK_UDIV(q, dv_ochunk);
-      uint32_t pos = i * GC + g * C + (q - i * C), f = 0;
-      if (A->P.n_frames > 1) {
-        const uint32_t r = RPK_UDIV(pos, dv_frames);
-        f = pos - r * A->P.n_frames;
-        pos = r;
-      }
-      const uint32_t u = A->P.unit_order[pos];
-      const uint32_t sl = RPK_UDIV(u, dv_nbatch);
-      batch = u - sl * A->P.nbatch + f * A->P.nbatch;  // (the unit carries its global batch)
-      slot = sl;
-      const uint32_t k = RPK_UDIV(sl, dv_tile_px), local = sl - k * tile_px;
-      const uint32_t dk = A->P.shard + k * A->P.nshards, t = A->P.tile_map ? A->P.tile_map[dk] : dk;
-      const uint32_t ty = RPK_UDIV(t, dv_tiles_x), tx = t - ty * A->P.tiles_x;
-      const uint32_t lj = RPK_UDIV(local, dv_tw), li = local - lj * tw;
-      pi = tx * tw + li;
-      pj = ty * th + lj;
-      if (pi < A->P.W && pj < A->P.H) return true;
-    }
-  }
-  // Per-XCD queues (rp.h RP_QUEUES_*): blocks blockIdx mod G share an XCD; their queue g serves the tiles
-  // k = g, g + G, ... of the order (or the g-th run of it), and once it is drained they take units from the
-  // next queues in turn.  Every fetch starts at the home queue: a drained queue costs one failed increment.
-  // The queue a wave increments is wave-uniform (`tries` moves for the whole wave once any lane finds the
-  // queue drained -- then it is drained for every lane), so the compiler folds the lanes' atomicAdd into one
-  // wave atomic (ballot + mbcnt); a per-lane atomic on one word cost C3 +35 %.
-  // several frames per launch: n_frames x n_shard_tiles virtual tiles (rp_kernel.h KParams::n_frames)
-  const uint32_t G = max(A->P.queue_groups, 1u), K = A->P.n_shard_tiles * (PROBE ? 1u : A->P.n_frames);
-  const uint32_t home = G > 1 ? blockIdx.x % G : 0u;
-  for (uint32_t tries = 0;;) {
-    uint32_t g = home + tries;
-    if (g >= G) g -= G;
-    g = __builtin_amdgcn_readfirstlane(g);
-    // queue g serves the chunks g, g + G, ... of C consecutive tiles of the order: tile k of its i-th unit
-    // run is (i / C) * G * C + g * C + i % C
-    const uint32_t C = A->P.queue_chunk, GC = G * C;
-    const uint32_t rest = K % GC, nk = (K / GC) * C + min(rest - min(rest, g * C), C);
-    const uint32_t q = atomicAdd(queue + g * QUEUE_STRIDE, 1u);
-    const bool drained = (uint64_t)q >= (uint64_t)nk * tile_units;
-    if (__ballot(drained) != 0) {
-      ++tries;
-      if (drained) {
-        if (tries >= G) return false;  // every queue drained
-        continue;
-      }
-    }
-    // (PROBE launches decode with plain divisions: one small launch)
-    uint32_t i = PROBE ? q / tile_units : RPK_UDIV(q, dv_units);
-    uint32_t rem = q - i * tile_units;
-    if (!PROBE && A->P.frames_inter == 2u) {
-      // RP_FRAME_ORDER_PIXEL: the n_frames consecutive virtual tiles of a queue's sequence (one shard tile of every
-      // frame) as one run of units with a unit's frames consecutive -- a wave holds ~64 / n_frames pixels x their frames
-      const uint32_t grp = RPK_UDIV(i, dv_frames);
-      const uint32_t o = (i - grp * A->P.n_frames) * tile_units + rem;
-      const uint32_t u = RPK_UDIV(o, dv_frames);
-      i = grp * A->P.n_frames + (o - u * A->P.n_frames);
-      rem = u;
-    }
-    const uint32_t ic = PROBE ? i / C : RPK_UDIV(i, dv_chunk);
-    uint32_t k = ic * GC + g * C + (i - ic * C);
-    // a tile's units pixel-major, a pixel's batches consecutive: a wave fetches 64 / nbatch pixels with all
-    // their batches, whose camera rays traverse nearly the same nodes (C3 -0.9 %, C5 -0.9 % against
-    // batch-major, ab32)
-    const uint32_t local = PROBE ? rem / A->P.nbatch : RPK_UDIV(rem, dv_nbatch);
-    batch = rem - local * A->P.nbatch;
-    if (!PROBE && A->P.n_frames > 1) {  // virtual tile -> frame f, its tile k; the unit carries its global batch
-      uint32_t f;
-      if (A->P.frames_inter) {
-        const uint32_t r = RPK_UDIV(k, dv_frames);
-        f = k - r * A->P.n_frames;
-        k = r;
-      } else {
-        f = RPK_UDIV(k, dv_tiles);
-        k -= f * A->P.n_shard_tiles;
-      }
-      batch += f * A->P.nbatch;
-    }
-    if (!PROBE && A->P.tile_order) k = A->P.tile_order[k];  // the queue hands out shard tiles in cost order
-    slot = k * tile_px + local;                     // output slot: shard tile order (rp_shard_unpack)
-    const uint32_t dk = A->P.shard + k * A->P.nshards, t = A->P.tile_map ? A->P.tile_map[dk] : dk;
-    const uint32_t ty = PROBE ? t / A->P.tiles_x : RPK_UDIV(t, dv_tiles_x), tx = t - ty * A->P.tiles_x;
-    const uint32_t lj = PROBE ? local / tw : RPK_UDIV(local, dv_tw), li = local - lj * tw;
-    pi = tx * tw + li;
-    pj = ty * th + lj;
-    if (pi < A->P.W && pj < A->P.H) return true;
-  }
-}
-
-// RNG contract (include/rp.h): batch b of pixel (i, j) is its own StdRng stream,
-// seed_from_u64(seed + b * W * H + j * W + i); batch 0 is the per-pixel stream of the original contract.
-RPK_INLINE uint64_t unit_seed(KArgsPtr A, uint32_t pi, uint32_t pj, uint32_t batch) {
-  return A->P.seed + (uint64_t)batch * A->P.W * A->P.H + (uint64_t)pj * A->P.W + pi;
-}
-// The frame of a unit's (global) batch and its batch within the frame (several frames per launch: KParams::n_frames).
-RPK_INLINE uint32_t unit_frame(KArgsPtr A, uint32_t batch) { return A->P.n_frames > 1 ? RPK_UDIV(batch, dv_nbatch) : 0u; }
-// Samples in this unit's batch.
-RPK_INLINE uint32_t unit_spp(KArgsPtr A, uint32_t batch) {
-  const uint32_t b = batch - unit_frame(A, batch) * A->P.nbatch;
-  return min(A->P.spp_batch, A->P.spp - b * A->P.spp_batch);
-}
+// What rp_units.h's unit fetch needs from the place it runs in, on the GPU (the host library has its own, rp_host.cpp).
+// All forced inline, so the fetch reaches the optimizer as the text it was when it stood here.
+struct DevEnv {
+  static RPK_INLINE KArgsPtr args() { return kargs(); }
+  static RPK_INLINE uint32_t fetch_add(unsigned int* p) { return atomicAdd(p, 1u); }
+  static RPK_INLINE bool any(bool x) { return __ballot(x) != 0; }
+  static RPK_INLINE uint32_t uniform(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+  static RPK_INLINE uint32_t block() { return blockIdx.x; }
+  static RPK_INLINE uint32_t numerator(uint32_t n) { return n; }
+};
 
 // Camera::shoot (render.rs:32-52) from the jittered frame coordinates (ju, jv) and the UnitDisk sample (dx, dy): one
 // definition for the path loop (start_sample) and the coherent primary pass, which passes (0, 0) -- with lens_radius 0

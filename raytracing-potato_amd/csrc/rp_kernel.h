@@ -64,7 +64,7 @@ enum {
 
 // Division by a launch constant d >= 1 of numerators n < 2^31 (Granlund & Montgomery 1994, Thm 4.2 with N = 31):
 // l = ceil(log2 d), s = 31 + l, m = ceil(2^s / d) < 2^32 (m d - 2^s < d <= 2^l), and floor(n / d) = (n m) >> s.
-// The unit decode of every fetch (rp_device.h fetch_pixel) divides by five per-launch values; the compiler's
+// The unit decode of every fetch (rp_units.h fetch_pixel) divides by five per-launch values; the compiler's
 // division by a run-time divisor is ~25 VALU each.
 struct Div32 {
   uint32_t m, s;

@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(BLOCK) RPK_RENDER_ATTR render_kernel(const KAr
   ts.bu = ts.bv = 0.0;
   ts.gy = ts.py = 0u;
   uint32_t pi = 0, pj = 0;
-  bool alive = fetch_pixel<PROBE>(slot, pi, pj, batch);
+  bool alive = fetch_pixel<PROBE, DevEnv>(slot, pi, pj, batch);
   pipj = pi | (pj << 16);
   bool tdone = true;  // traversal of the current ray finished (or no ray)
   bool newray = false;  // a ray started since the last traversal round (always-tested prims pending)
@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(BLOCK) RPK_RENDER_ATTR render_kernel(const KAr
             rays_pix = lane_rays;
           })
           uint32_t pi = 0, pj = 0;
-          alive = fetch_pixel<PROBE>(slot, pi, pj, batch);
+          alive = fetch_pixel<PROBE, DevEnv>(slot, pi, pj, batch);
           pipj = pi | (pj << 16);
           DIAG(if (!alive) t_retire = __builtin_amdgcn_s_memrealtime();)
           DIAG(if (!PROBE && !alive) atomicMax(&A->diag[11], ~(unsigned long long)__builtin_amdgcn_s_memrealtime());)
@@ -440,6 +440,8 @@ __global__ void __launch_bounds__(256) reduce_batches_kernel(const KParams P, do
                                                             float* __restrict__ out_fg) {
   const uint64_t slot = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (slot >= P.n_slots) return;
+  // (rp_units.h slot_pixel's decode, written out: through the helper the two frame tests become one branch, which is
+  // not the instruction stream the build id stands for -- profiles/r12/MANIFEST.md)
   const uint32_t tile_px = P.tw * P.th, k = (uint32_t)(slot / tile_px), local = (uint32_t)(slot % tile_px);
   const uint32_t dk = P.shard + k * P.nshards, t = P.tile_map ? P.tile_map[dk] : dk;
   if ((t % P.tiles_x) * P.tw + local % P.tw >= P.W || (t / P.tiles_x) * P.th + local / P.tw >= P.H) return;

@@ -148,7 +148,8 @@ class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launc
 
 HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save", "rph_free", "rph_to_srgb_u8",
                 "rph_lookat", "rph_sky_panorama", "rph_bvh_selfcheck", "rph_bvh_traversal_stats", "rph_bvh_selfcheck_ex", "rph_bvh_traversal_stats_ex", "rph_bvh_tree_hash", "rph_last_error",
-                "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test"]
+                "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test",
+                "rph_unit_walk"]
 
 
 def rp_lib_path() -> str:
@@ -279,6 +280,8 @@ def host() -> ctypes.CDLL:
     lib.rph_ray_setup.argtypes = [c_uint32, c_double, c_void_p, c_uint64, c_void_p]
     lib.rph_prim_test.argtypes = [c_uint32, c_void_p, c_void_p, c_uint64, c_void_p]
     lib.rph_plan_launch.argtypes = [c_uint32] * 14 + [c_uint64, POINTER(rph_launch_plan)]
+    lib.rph_unit_walk.argtypes = [c_uint32] * 14 + [c_void_p] * 3 + [c_uint32] * 4 + [c_void_p, c_uint64,
+                                  POINTER(c_uint64), c_void_p, c_void_p, POINTER(c_uint64)]
     _host = lib
     return lib
 

@@ -173,7 +173,7 @@ def test_c4_balanced_shard_against_oracle(gpu):
 
 def test_shards_of_2_31_units_are_refused(gpu):
     """The unit decode divides by launch constants with 31-bit multiply-shift magic numbers (rp_kernel.h make_div32,
-    rp_device.h fetch_pixel), so rp_schedule.h (plan_launch) refuses a shard of 2^31 or more (pixel, sample batch) units with RP_EINVAL
+    rp_units.h fetch_pixel), so rp_schedule.h (plan_launch) refuses a shard of 2^31 or more (pixel, sample batch) units with RP_EINVAL
     before anything is launched: here 8192 x 8192 pixels x 32 batches of 32 samples on one unit queue (per-XCD queues
     hit the 2^32 queue-word limit first)."""
     import torch

@@ -1,4 +1,4 @@
-"""Several frames per persistent launch (include/rp.h rp_render_frames_device_ws, rp_device.h fetch_pixel).
+"""Several frames per persistent launch (include/rp.h rp_render_frames_device_ws, rp_units.h fetch_pixel).
 
 Frame f of a launch of n_frames is, by the contract, the frame rp_render_device renders with seed + f * B * W * H
 (B = the frame's sample batches): every unit is seeded by its pixel and its global batch, so the schedule -- units of

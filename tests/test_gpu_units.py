@@ -1,4 +1,4 @@
-"""The learned per-unit order (rp_scene_options.unit_order, rp_sched.hip; rp_device.h fetch_pixel).
+"""The learned per-unit order (rp_scene_options.unit_order, rp_sched.hip; rp_units.h fetch_pixel).
 
 A render of one frame per launch stores every unit's duration; the next frame of the same shape on the workspace hands
 its units out longest first.  Units are seeded by pixel and batch, so a different schedule must give the

@@ -1,5 +1,5 @@
 """The unit decode's division by launch constants (raytracing-potato_amd/csrc/rp_kernel.h make_div32, used by
-rp_device.h fetch_pixel): floor(n / d) = (n * m) >> s with l = ceil(log2 d), s = 31 + l, m = ceil(2^s / d), for every
+rp_units.h fetch_pixel): floor(n / d) = (n * m) >> s with l = ceil(log2 d), s = 31 + l, m = ceil(2^s / d), for every
 numerator n < 2^31 (rp_schedule.h refuses shards of >= 2^31 units).  The header's own function (through the
 librp_host.so test hook rph_make_div32, compiled from the same rp_kernel.h) is checked against Python's integer
 division over edge and random cases, and against a restatement of its arithmetic; the GPU parity tests exercise the

@@ -6,6 +6,7 @@
 //     (rph_bvh_tree_hash: the tree must not depend on the thread count) and the structural self-check, on a random
 //     triangle soup, a mesh with shared vertices and degenerate (zero-area, duplicated) triangles, and spheres;
 //   - the CPU traversal model (rph_bvh_traversal_stats_ex) and the exact primitive tests (rph_prim_test) over random rays;
+//   - the render kernel's unit fetch in its host environment (rph_unit_walk: csrc/rp_units.h);
 //   - the OBJ and TGA readers (mesh.rs:145-183, image.rs:73-114) on files this driver writes, including truncated and
 //     malformed ones (they must fail cleanly), and the TGA writer;
 //   - the bulk StdRng (rph_stdrng_u64, threaded) against the oracle's sequential stream;
@@ -291,9 +292,31 @@ static void check_plan() {
   std::printf("launch plans: %d planned, %d refused\n", planned, refused);
 }
 
+// the render kernel's unit fetch in the host environment (csrc/rp_units.h, rph_unit_walk): the ragged frame, three
+// frames per launch in pixel order over the per-XCD queues, with the wave-mate vote forced; and its cost probe
+static void check_unit_walk() {
+  const uint32_t W = 37, H = 21, nbatch = 3, frames = 3, blocks = 11;
+  std::vector<uint32_t> units((size_t)RPH_UNIT_WORDS * 30 * 32 * nbatch * frames), words(RPH_QUEUE_WORDS),
+      entries(RPH_QUEUE_WORDS);
+  const uint64_t cap = units.size() / RPH_UNIT_WORDS;
+  uint64_t n = 0, forced = 0;
+  for (uint32_t lattice : {0u, 3u}) {
+    CHECK(rph_unit_walk(W, H, 5, 8, 8, 4, 0, 1, 2, 0, frames, RP_FRAME_ORDER_PIXEL, RP_QUEUES_XCD_TILES, 3, nullptr, nullptr,
+                        nullptr, lattice, 0, blocks, lattice ? 0 : 1, units.data(), cap, &n, words.data(), entries.data(),
+                        &forced) == RP_OK);
+    CHECK(n == (lattice ? 30ull * lattice * lattice : (uint64_t)W * H * nbatch * frames));
+    for (uint64_t u = 0; u < n; u++) CHECK(units[RPH_UNIT_WORDS * u + 1] < W && units[RPH_UNIT_WORDS * u + 2] < H);
+    if (!lattice) CHECK(forced >= 1);
+  }
+  CHECK(rph_unit_walk(W, H, 5, 8, 8, 4, 0, 1, 2, 0, frames, RP_FRAME_ORDER_PIXEL, RP_QUEUES_XCD_TILES, 3, nullptr, nullptr,
+                      nullptr, 0, 0, blocks, 0, units.data(), 10, &n, words.data(), entries.data(), &forced) == RP_EINVAL);
+  std::printf("unit walk: every unit of three ragged frames fetched, probe lattice walked, a short buffer refused\n");
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
   check_plan();
+  check_unit_walk();
   MeshScene a = soup(200000, 11);  // >= 2^16 primitives: the parallel build form (rp_bvh.cpp ParallelBuild) runs
   check_tree("soup", a.desc);
   MeshScene b = grid_with_degenerates(40, 3);
