@@ -447,6 +447,56 @@ int rp_render_aov_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_c
 int rp_render_aov(rp_scene* scene, const rp_camera* camera, const rp_render_params* params, double* out_normal,
                   double* out_albedo, double* out_depth, float* out_fg, rp_stats* stats);
 
+/* Guided denoiser for low-spp frames: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) that
+ * takes the beauty frame and the feature pass's noiseless guides (rp_render_aov) and returns a picture.  The reference
+ * has none (render.rs:101 only leaves the hook), so the definition is this project's own; DESIGN.md 4.11.
+ *   Buffers are FULL FRAMES IN FRAME ORDER: row-major, pixel (i, j) at j*width + i, row 0 = bottom, as
+ *   rp_frame_assemble leaves them -- rgb, normal, albedo 3 doubles per pixel, depth 1, exactly as rp_render and
+ *   rp_render_aov define them.  Everything is IEEE binary64, uses only + - * /, comparisons and max, and is evaluated
+ *   in the order written here without contraction: the device, librp_host.so's rph_denoise and a numpy model agree to
+ *   the last bit.
+ *   Parameters: a zero field takes its default (rp_denoise_params_init fills them in), params = NULL means all defaults.
+ *     iterations    3     L, 1..8
+ *     normal_power  6     e_n, 1..8: the normal weight is cos^(2^e_n)
+ *     sigma_depth   0.05  sigma_z   (> 0)
+ *     sigma_albedo  0.1   sigma_a   (> 0)
+ *     sigma_color   1.0   sigma_c; negative disables the colour term
+ *     albedo_eps    1e-2  eps       (> 0)
+ *   Per pixel: nn = (n.x*n.x + n.y*n.y) + n.z*n.z; c = rgb / (albedo + eps) per channel (demodulation);
+ *   rat(x2) = 1 / ((1 + x2) * (1 + x2)).  Squared lengths and dot products are summed as nn is.
+ *   Level l = 0 .. L-1 has step s = 2^l and colour scale sigma_c,l = sigma_c / 2^l.  For pixel p the taps run
+ *   dy = -2..2 (outer), dx = -2..2 (inner), q = p + s*(dx, dy); a tap outside the frame is skipped;
+ *   h = k[|dx|] * k[|dy|], k = {3/8, 1/4, 1/16}.
+ *     w_n: d = n_p . n_q, ab = nn_p * nn_q; ab > 0 and d > 0: (d*d)/ab squared e_n - 1 times; else 0; centre tap: 1.
+ *     w_z: m = max(|z_p|, |z_q|); x = m > 0 ? (z_p - z_q) / (sigma_z * m) : 0; w_z = rat(x*x).
+ *     w_a = rat(|a_p - a_q|^2 / (sigma_a*sigma_a)).
+ *     w_c = rat(|c_p - c_q|^2 / (sigma_c,l*sigma_c,l)) with c the level's input, or 1 when disabled.
+ *     w = (((h * w_n) * w_z) * w_a) * w_c; sw += w and acc += w * c_q from 0.0 in tap order; c' = acc / sw.
+ *   A pixel with nn == 0 (background, misses: its radiance is the emission itself) keeps its c through every level and
+ *   is never a neighbour's tap (w_n = 0).  After the last level out = c * (albedo + eps); a pixel with nn == 0 gets rgb
+ *   itself, bit for bit.  Missing guides: albedo NULL -- no demodulation, w_a = 1; normal NULL -- w_n = 1 and no
+ *   pass-through; depth NULL -- w_z = 1.  NaN inputs propagate.
+ *   Known limit: first-hit guides say nothing about what a mirror or a glass surface shows, so there sigma_c is the only
+ *   edge stop, and on such frames at 16 spp the filter can lose to the noisy frame.
+ * rp_denoise_device: asynchronous on `stream` on the CURRENT device (as rp_frame_assemble); one kernel launch per level,
+ * no allocation and no synchronisation inside (capturable, like rp_render_device).  d_scratch: rp_denoise_scratch_bytes
+ * bytes of device memory, 8-byte aligned (two colour buffers the levels ping-pong between; host only, needs no device).
+ * d_out must not alias an input (nor scratch anything): RP_EINVAL, as are NULL rgb, out or scratch, a zero size, a side
+ * above 65535 and parameters out of range.
+ * rp_denoise: the synchronous version from and to host buffers on `device`; seconds (nullable) = device time of the
+ * levels (HIP events). */
+typedef struct rp_denoise_params {
+  uint32_t iterations, normal_power;
+  double sigma_depth, sigma_albedo, sigma_color, albedo_eps;
+} rp_denoise_params;
+int rp_denoise_params_init(rp_denoise_params* params);
+int rp_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+int rp_denoise_device(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* d_rgb,
+                      const double* d_normal, const double* d_albedo, const double* d_depth, double* d_out,
+                      void* d_scratch, void* stream);
+int rp_denoise(const rp_denoise_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
+               const double* normal, const double* albedo, const double* depth, double* out, double* seconds);
+
 /* Output stage on the device: the reference's to_srgb_u8 (utility.rs:212-220, alpha 255) of every slot of
  * a compact shard buffer, bytes in tga::save's pixel order B, G, R, A (image.rs:116-137), so a gathered
  * and de-interleaved frame is the body of the reference's output.tga (18-byte header: rph_tga_save).

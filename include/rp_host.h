@@ -157,6 +157,13 @@ int rph_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bo
                   uint32_t n_blocks, uint32_t any_every, uint32_t* units, uint64_t units_cap, uint64_t* n_units,
                   uint32_t* queue_words, uint32_t* entries, uint64_t* forced);
 
+/* The guided denoiser on the CPU (include/rp.h rp_denoise: the definition): a plain loop over
+ * raytracing-potato_amd/csrc/rp_denoise.h, the same header the device kernel compiles, so the two agree bit for bit.
+ * Host buffers, full frames in frame order; params, normal, albedo and depth nullable as rp_denoise's.  RP_EINVAL for
+ * NULL rgb or out, a zero size, a side above 65535, out aliasing an input and parameters out of range. */
+int rph_denoise(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* rgb, const double* normal,
+                const double* albedo, const double* depth, double* out);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

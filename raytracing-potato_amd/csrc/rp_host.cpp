@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "rp_bvh.h"
+#include "rp_denoise.h"
 #include "rp_draw.h"
 #include "rp_isect.h"
 #include "rp_kernel.h"
@@ -986,6 +987,66 @@ int rph_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bo
   *forced = W.forced;
   if (W.err) return fail(W.err);
   if (*n_units > units_cap) return fail("rph_unit_walk: more units than units_cap");
+  return RP_OK;
+}
+
+// The denoiser's levels as a plain loop over rp_denoise.h (what rp_denoise.hip's kernel does per lane): demodulate once,
+// every level from one colour buffer into the other, remodulate (or copy a pass-through pixel's rgb) at the end.
+int rph_denoise(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* rgb, const double* normal,
+                const double* albedo, const double* depth, double* out) {
+  if (width == 0 || height == 0 || width > 65535 || height > 65535)
+    return fail("rph_denoise: width and height must be 1..65535");
+  if (!rgb || !out) return fail("rph_denoise: rgb and out must be non-NULL");
+  rp_denoise_params P;
+  if (!rpdn::resolve(params, P))
+    return fail("rph_denoise: params out of range (iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo and "
+                "albedo_eps > 0 and finite, sigma_color finite)");
+  const uint64_t n = (uint64_t)width * height;
+  auto overlaps = [&](const double* in, uint64_t channels) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(out), y = reinterpret_cast<uintptr_t>(in);
+    return in && x < y + 8 * channels * n && y < x + 24 * n;
+  };
+  if (overlaps(rgb, 3) || overlaps(normal, 3) || overlaps(albedo, 3) || overlaps(depth, 1))
+    return fail("rph_denoise: out must not alias an input");
+  std::vector<double> cur(3 * n), nxt(3 * n);
+  auto pixel = [&](const std::vector<double>& c, uint64_t i) {
+    rpdn::Px p = {};
+    p.cx = c[3 * i], p.cy = c[3 * i + 1], p.cz = c[3 * i + 2];
+    if (normal) {
+      p.nx = normal[3 * i], p.ny = normal[3 * i + 1], p.nz = normal[3 * i + 2];
+      p.nn = rpdn::len2(p.nx, p.ny, p.nz);
+    }
+    if (albedo) p.ax = albedo[3 * i], p.ay = albedo[3 * i + 1], p.az = albedo[3 * i + 2];
+    if (depth) p.z = depth[i];
+    return p;
+  };
+  for (uint64_t i = 0; i < 3 * n; i++) cur[i] = albedo ? rpdn::demod(rgb[i], albedo[i], P.albedo_eps) : rgb[i];
+  rpdn::Level L{};
+  for (uint32_t l = 0; l < P.iterations; l++) {
+    L = rpdn::make_level(P, l, normal != nullptr, albedo != nullptr, depth != nullptr);
+    const int64_t s = L.step;
+    for (uint32_t j = 0; j < height; j++)
+      for (uint32_t i = 0; i < width; i++) {
+        const uint64_t at = (uint64_t)j * width + i;
+        rpdn::level_step(
+            L, pixel(cur, at),
+            [&](int dx, int dy, rpdn::Px& q) {
+              const int64_t qi = (int64_t)i + s * dx, qj = (int64_t)j + s * dy;
+              if (qi < 0 || qi >= (int64_t)width || qj < 0 || qj >= (int64_t)height) return false;
+              q = pixel(cur, (uint64_t)qj * width + (uint64_t)qi);
+              return true;
+            },
+            nxt[3 * at], nxt[3 * at + 1], nxt[3 * at + 2]);
+      }
+    cur.swap(nxt);
+  }
+  for (uint64_t at = 0; at < n; at++) {
+    const rpdn::Px p = pixel(cur, at);
+    for (int k = 0; k < 3; k++) {
+      const uint64_t i = 3 * at + k;
+      out[i] = rpdn::passes(L, p) ? rgb[i] : (albedo ? rpdn::remod(cur[i], albedo[i], P.albedo_eps) : cur[i]);
+    }
+  }
   return RP_OK;
 }
 

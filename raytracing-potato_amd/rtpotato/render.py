@@ -261,6 +261,45 @@ class DeviceScene:
         F.check(F.rp().rp_render_aov_device_ws(self.handle, workspace.handle if workspace else None, ctypes.byref(cam),
                                                ctypes.byref(p), *ptr, ctypes.c_void_p(s.cuda_stream)))
 
+    # ---- beauty + guides + denoiser, device-resident ---------------------------------------------------
+    def render_denoised(self, params: RenderParams, denoise=None, bgra: bool = False, camera=None, stream=None):
+        """A denoised frame without a host round trip: the beauty render and the feature pass into shard buffers,
+        rp_frame_assemble at num_shards = 1 into frame order, then rp_denoise_device (`denoise`: rp_denoise_params, a
+        dict of its fields or None = the defaults), all on `stream` (torch stream; default: current).  Returns the frame
+        as a torch f64 tensor (h, w, 3) on the scene's device and, with bgra=True, also its to_srgb_u8 bytes (h, w, 4)
+        uint8 in TGA order B, G, R, A (rp_shard_to_bgra8: a frame-order buffer is the shard buffer of the frame tiled
+        tile_w = width, tile_h = height).  One device holds the whole frame (multi-GPU frames assemble with
+        rp_frame_assemble_ws and denoise_device)."""
+        import torch
+        from dataclasses import replace
+        if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
+            raise ValueError("render_denoised renders the whole frame on one device (num_shards = 1, interleave)")
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        w, h, n = params.width, params.height, shard_slot_count(params)
+        self.reserve(params)
+        with torch.cuda.stream(s):
+            shard = {k: torch.empty(c * n, dtype=torch.float64, device=dev)
+                     for k, c in (("rgb", 3), ("normal", 3), ("albedo", 3), ("depth", 1))}
+            frame = {k: torch.empty(c * w * h, dtype=torch.float64, device=dev)
+                     for k, c in (("rgb", 3), ("normal", 3), ("albedo", 3), ("depth", 1))}
+            ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
+            out = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+            self.render_device(params, shard["rgb"], ctr, camera=camera, stream=s)
+            self.render_aov_device(params, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
+                                   camera=camera, stream=s)
+            p = params.to_c()
+            for k, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
+                F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 2 * (t.numel() // n),
+                                                 frame[k].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+            denoise_device(frame["rgb"], frame["normal"], frame["albedo"], frame["depth"], out, params=denoise,
+                           stream=s)
+            if not bgra:
+                return out
+            bytes_ = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+            self.to_bgra8(replace(params, tile_w=w, tile_h=h), out, bytes_, stream=s)
+            return out, bytes_
+
     def to_bgra8(self, params: RenderParams, shard_rgb, out, stream=None) -> None:
         """Output stage on the device (rp_shard_to_bgra8): the shard's linear f64 RGB (`shard_rgb`, torch
         f64) -> to_srgb_u8 bytes in TGA order B, G, R, A into `out` (torch uint8, >= 4 * slots)."""
@@ -476,6 +515,98 @@ def srgb_thresholds() -> np.ndarray:
     t = np.empty(256, dtype=np.float64)
     F.check(F.rp().rp_srgb_thresholds(t.ctypes.data))
     return t
+
+
+# ---- guided denoiser (rp_denoise*, include/rp.h) --------------------------------------
+def denoise_params(params=None, **kw) -> F.rp_denoise_params:
+    """rp_denoise_params: `params` (an rp_denoise_params, a dict of its fields or None) with fields overridden by
+    keyword.  Fields left at zero take the library's defaults (iterations 3, normal_power 6, sigma_depth 0.05,
+    sigma_albedo 0.1, sigma_color 1.0 -- negative disables the colour term --, albedo_eps 1e-2)."""
+    p = F.rp_denoise_params()
+    if isinstance(params, F.rp_denoise_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    elif params:
+        kw = {**params, **kw}
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(f"unknown denoise parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_defaults() -> F.rp_denoise_params:
+    """rp_denoise_params_init: every field at its default (host only)."""
+    p = F.rp_denoise_params()
+    F.check(F.rp().rp_denoise_params_init(ctypes.byref(p)))
+    return p
+
+
+def denoise_scratch_bytes(width: int, height: int) -> int:
+    """rp_denoise_scratch_bytes: device bytes denoise_device needs beside its buffers (host only)."""
+    b = ctypes.c_uint64()
+    F.check(F.rp().rp_denoise_scratch_bytes(width, height, ctypes.byref(b)))
+    return b.value
+
+
+def _host_frames(rgb, normal, albedo, depth):
+    rgb = np.ascontiguousarray(rgb, dtype=np.float64)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3, "rgb: (h, w, 3)"
+    h, w = rgb.shape[:2]
+    guides = []
+    for name, g, shape in (("normal", normal, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("depth", depth, (h, w))):
+        if g is not None:
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            assert g.shape == shape, f"{name}: {shape}, got {g.shape}"
+        guides.append(g)
+    return rgb, guides, h, w
+
+
+def denoise(rgb, normal=None, albedo=None, depth=None, params=None, device: int = 0):
+    """rp_denoise on host arrays in frame order -- rgb, normal, albedo (h, w, 3), depth (h, w), each guide optional --
+    through the device kernel: (denoised (h, w, 3) f64, device seconds of the levels)."""
+    rgb, guides, h, w = _host_frames(rgb, normal, albedo, depth)
+    p = denoise_params(params)
+    out = np.empty_like(rgb)
+    sec = ctypes.c_double()
+    F.check(F.rp().rp_denoise(ctypes.byref(p), device, w, h, rgb.ctypes.data,
+                              *[g.ctypes.data if g is not None else None for g in guides], out.ctypes.data,
+                              ctypes.byref(sec)))
+    return out, sec.value
+
+
+def denoise_host(rgb, normal=None, albedo=None, depth=None, params=None) -> np.ndarray:
+    """rph_denoise: the same filter on the CPU (librp_host.so; the same arithmetic header as the kernel, equal bits)."""
+    rgb, guides, h, w = _host_frames(rgb, normal, albedo, depth)
+    p = denoise_params(params)
+    out = np.empty_like(rgb)
+    F.check_host(F.host().rph_denoise(ctypes.byref(p), w, h, rgb.ctypes.data,
+                                      *[g.ctypes.data if g is not None else None for g in guides], out.ctypes.data))
+    return out
+
+
+def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, stream=None) -> None:
+    """rp_denoise_device on torch tensors of one device, asynchronously on `stream` (torch stream; default: current):
+    rgb (h, w, 3) f64 and the optional guides normal, albedo (h, w, 3), depth (h, w) in frame order (flat tensors of
+    the same sizes are taken with `out`'s shape), `out` (h, w, 3) f64, which must not alias an input.  scratch: a
+    tensor of >= denoise_scratch_bytes(w, h) bytes (default: allocated here on `stream`)."""
+    import torch
+    assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.dim() == 3 and out.shape[2] == 3
+    h, w = out.shape[:2]
+    for t, m in ((rgb, 3 * w * h), (normal, 3 * w * h), (albedo, 3 * w * h), (depth, w * h)):
+        if t is not None:
+            assert t.dtype == torch.float64 and t.device == out.device and t.is_contiguous() and t.numel() == m
+    assert rgb is not None
+    s = stream if stream is not None else torch.cuda.current_stream(out.device)
+    need = denoise_scratch_bytes(w, h)
+    if scratch is None:
+        with torch.cuda.stream(s):
+            scratch = torch.empty(need // 8, dtype=torch.float64, device=out.device)
+    assert scratch.is_cuda and scratch.device == out.device and scratch.numel() * scratch.element_size() >= need
+    p = denoise_params(params)
+    with torch.cuda.device(out.device):
+        F.check(F.rp().rp_denoise_device(ctypes.byref(p), w, h, rgb.data_ptr(),
+                                         *[t.data_ptr() if t is not None else None for t in (normal, albedo, depth)],
+                                         out.data_ptr(), scratch.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
 
 
 def tga_bytes(width: int, height: int, bgra) -> bytes:

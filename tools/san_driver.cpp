@@ -313,10 +313,38 @@ static void check_unit_walk() {
   std::printf("unit walk: every unit of three ragged frames fetched, probe lattice walked, a short buffer refused\n");
 }
 
+// the guided denoiser's host loop (csrc/rp_denoise.h, rph_denoise) on a 7 x 5 frame at L = 5: most taps leave the frame,
+// two pixels are misses (zero normal), and a depth is zero
+static void check_denoise() {
+  const uint32_t W = 7, H = 5;
+  std::vector<double> rgb(3 * W * H), nrm(3 * W * H), alb(3 * W * H), dep(W * H), out(3 * W * H), out2(3 * W * H);
+  for (uint32_t i = 0; i < W * H; i++) {
+    const bool miss = i == 3 || i == 17;
+    for (int k = 0; k < 3; k++) {
+      rgb[3 * i + k] = 0.1 + 0.01 * ((i * 7 + k * 3) % 11);
+      nrm[3 * i + k] = miss ? 0.0 : (k == (int)(i / 12) % 3 ? 1.0 : 0.1);
+      alb[3 * i + k] = miss ? 0.0 : 0.5 + 0.1 * k;
+    }
+    dep[i] = miss || i == 9 ? 0.0 : 2.0 + 0.05 * i;
+  }
+  rp_denoise_params p{};
+  p.iterations = 5;
+  CHECK(rph_denoise(&p, W, H, rgb.data(), nrm.data(), alb.data(), dep.data(), out.data()) == RP_OK);
+  for (uint32_t i : {3u, 17u})
+    for (int k = 0; k < 3; k++) CHECK(out[3 * i + k] == rgb[3 * i + k]);
+  for (double x : out) CHECK(x > 0.0 && x < 1.0);
+  CHECK(rph_denoise(nullptr, W, H, rgb.data(), nullptr, nullptr, nullptr, out2.data()) == RP_OK);
+  CHECK(rph_denoise(&p, W, H, rgb.data(), nrm.data(), alb.data(), dep.data(), rgb.data()) == RP_EINVAL);
+  p.iterations = 9;
+  CHECK(rph_denoise(&p, W, H, rgb.data(), nrm.data(), alb.data(), dep.data(), out.data()) == RP_EINVAL);
+  std::printf("denoise: 7 x 5 at five levels, misses passed through, aliasing and a bad level count refused\n");
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
   check_plan();
   check_unit_walk();
+  check_denoise();
   MeshScene a = soup(200000, 11);  // >= 2^16 primitives: the parallel build form (rp_bvh.cpp ParallelBuild) runs
   check_tree("soup", a.desc);
   MeshScene b = grid_with_degenerates(40, 3);
