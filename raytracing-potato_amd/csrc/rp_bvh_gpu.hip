@@ -3,16 +3,19 @@
 //
 // Replaces Bvh::new / make_bvh / split (bvh.rs:36-91) like the host builder does: the tree shape is not
 // part of the contract, only the packed layout of rp_layout.h, which is identical, so
-// the render and intersect kernels run unchanged.  Pipeline (Karras 2012 LBVH, then a wide collapse):
-//   1. 30-bit Morton code of each primitive's box centroid, key = code << 32 | primitive (unique keys);
-//   2. device radix sort of the keys (hipCUB);
-//   3. one thread per inner node finds its key range and split (the binary radix tree of Karras 2012);
-//   4. bottom-up f64 boxes: each leaf walks to the root, the second arrival at a node unions its
-//      children's boxes (the exact min/max of AABB::union, utility.rs:130-135);
-//   5. collapse into 4-wide nodes, one launch per level: a wide node takes its binary node's children
-//      and opens the inner child of largest surface area until it has four (the host collapser's rule);
-//      a subtree of <= max_leaf primitives -- a contiguous run of the sorted order -- becomes a leaf;
-//   6. primitive records permuted into leaf (= sorted) order; child boxes rounded outward to f32.
+// the render and intersect kernels run unchanged.  Two builders make a binary tree over the primitives in Morton
+// order, and one kernel collapses either tree into 4-wide nodes:
+//   build_gpu   the prologue: the upload, a Morton code of each box centroid, a device radix sort (hipCUB);
+//   build_lbvh  Karras 2012: 30-bit codes, key = code << 32 | primitive (unique keys); one thread per inner node finds
+//               its key range and split (the binary radix tree); bottom-up f64 boxes: each leaf walks to the root, the
+//               second arrival at a node unions its children's boxes (AABB::union's exact min/max, utility.rs:130-135);
+//   build_ploc  Meister & Bittner 2018: 63-bit codes; mutual nearest neighbours under the SAH distance merge, round by
+//               round, and every merge decides by the SAH whether its subtree becomes one leaf;
+//   collapse    collapse_kernel<NF, Src>, one launch per level: a wide node takes its binary node's children and opens
+//               the inner child of largest surface area until it has four (the host collapser's rule); child boxes
+//               rounded outward to f32 or quantized in the node's frame.  Src is the binary tree: RadixSrc or PlocSrc;
+//   last        the primitive records permuted into leaf order; the PLOC tree's nodes renumbered depth-first.
+// Every device buffer is a DevBuf, freed on every path; build_gpu releases the three outputs to the caller on success.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -22,6 +25,7 @@
 #include <vector>
 
 #include "rp_bvh.h"
+#include "rp_hip_util.h"
 
 namespace rpg {
 
@@ -32,6 +36,38 @@ constexpr uint32_t BIN_LEAF = 0x80000000u;  // binary child reference: leaf (sor
 struct Box6 {
   double lo[3], hi[3];
 };
+
+template <uint32_t NF>
+using NodeOf = typename std::conditional<NF == rpl::NODES_Q8, rpl::Node4Q, rpl::Node4>::type;
+
+// f(integral_constant<NF>) for the node format: the one place a format picks a kernel instantiation
+template <class F>
+void with_format(uint32_t node_format, F&& f) {
+  if (node_format == rpl::NODES_Q8) f(std::integral_constant<uint32_t, rpl::NODES_Q8>{});
+  else f(std::integral_constant<uint32_t, rpl::NODES_F32>{});
+}
+
+int failed(std::string& err, int code, const std::string& msg) {
+  err = msg;
+  return code;
+}
+
+// The file's one check: a failed HIP call (e) or launch ends the build with "<what>: <HIP's message>" in `err`.
+#define RPG_CHECK(what)                                                                                          \
+  do {                                                                                                           \
+    if (e == hipSuccess) e = hipGetLastError();                                                                  \
+    if (e != hipSuccess) return failed(err, RP_EHIP, std::string(what) + ": " + hipGetErrorString(e));           \
+  } while (0)
+
+// n elements for `buf` unless an earlier allocation of the chain failed already (e keeps the first failure)
+template <class T>
+void alloc(hipError_t& e, DevBuf<T>& buf, uint64_t n) {
+  if (e == hipSuccess) buf.alloc(n, &e);
+}
+
+int alloc_failed(const char* build, hipError_t e, std::string& err) {
+  return failed(err, RP_ENOMEM, std::string("hipMalloc (") + build + "): " + hipGetErrorString(e));
+}
 
 __device__ __forceinline__ uint32_t expand_bits10(uint32_t v) {  // 10 bits -> every third bit of 30
   v = (v * 0x00010001u) & 0xFF0000FFu;
@@ -187,37 +223,61 @@ __device__ __forceinline__ double area(const Box6& b) {  // rp_bvh.cpp Box::area
   return 2.0 * (dx * dy + dy * dz + dz * dx);
 }
 
-struct Frontier {
-  uint32_t bin;   // binary inner node
-  uint32_t wide;  // its wide node
-};
-
-__device__ __forceinline__ uint32_t bin_count(uint32_t c, const uint32_t* first, const uint32_t* last) {
-  return (c & BIN_LEAF) ? 1u : last[c] - first[c] + 1u;
+__device__ __forceinline__ Box6 box_union(const Box6& a, const Box6& b) {
+  Box6 u;
+  for (int c = 0; c < 3; c++) {
+    u.lo[c] = fmin(a.lo[c], b.lo[c]);
+    u.hi[c] = fmax(a.hi[c], b.hi[c]);
+  }
+  return u;
 }
 
-// One level of the collapse: every frontier entry fills its wide node and appends its inner wide
-// children to the next frontier.
-template <uint32_t NF>
-__global__ void collapse_kernel(const Frontier* __restrict__ cur, uint32_t n_cur, Frontier* __restrict__ next,
+// ---------------------------------------------------------------------------------------------------------------
+// The wide collapse, for either binary tree.  A child reference c is BIN_LEAF | x (one primitive) or a binary inner
+// node's id.  The tree is a Src (RadixSrc here, PlocSrc below), passed to the kernel by value.  It answers for a c:
+// left(c) and right(c), an inner node's children; is_leaf(c), whether c becomes one leaf of the wide tree (never
+// opened); count(c) and box(c), its primitives and their box; place_leaf(c, off), which puts a leaf child's primitives
+// into the leaf order and returns the leaf entry's first index (off: the first primitive slot of c's subtree).
+struct Frontier {
+  uint32_t bin, wide, poff;  // binary inner node, its wide node, the first primitive slot of its subtree (PlocSrc)
+};
+
+// The LBVH's radix tree: arrays over the inner nodes, leaves are sorted positions.  A subtree of <= max_leaf primitives
+// is a contiguous run of the sorted order, which is the leaf order already.
+struct RadixSrc {
+  static constexpr const char* stage = "collapse";
+  static constexpr const char* build = "device BVH build";
+  const uint32_t *__restrict__ lefts, *__restrict__ rights, *__restrict__ first, *__restrict__ last;
+  const uint32_t* __restrict__ order;
+  const Box6 *__restrict__ leaf_boxes, *__restrict__ node_boxes;
+  uint32_t max_leaf;
+  __device__ uint32_t left(uint32_t c) const { return lefts[c]; }
+  __device__ uint32_t right(uint32_t c) const { return rights[c]; }
+  __device__ uint32_t count(uint32_t c) const { return (c & BIN_LEAF) ? 1u : last[c] - first[c] + 1u; }
+  __device__ bool is_leaf(uint32_t c) const { return count(c) <= max_leaf; }
+  __device__ Box6 box(uint32_t c) const { return (c & BIN_LEAF) ? leaf_boxes[order[c & ~BIN_LEAF]] : node_boxes[c]; }
+  __device__ uint32_t place_leaf(uint32_t c, uint32_t) const { return (c & BIN_LEAF) ? (c & ~BIN_LEAF) : first[c]; }
+};
+
+// One level of the collapse: every frontier entry fills its wide node and appends its inner wide children to the next
+// frontier.
+template <uint32_t NF, class Src>
+__global__ void collapse_kernel(const Src src, const Frontier* __restrict__ cur, uint32_t n_cur,
+                                Frontier* __restrict__ next,
                                 uint32_t* __restrict__ counters /* [0] wide nodes, [1] next frontier, [2] leaves */,
-                                uint32_t max_leaf, const Box6* __restrict__ leaf_boxes,
-                                const uint32_t* __restrict__ order, const uint32_t* __restrict__ left,
-                                const uint32_t* __restrict__ right, const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ last, const Box6* __restrict__ node_boxes,
                                 void* __restrict__ nodes) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_cur) return;
   const Frontier f = cur[t];
-  uint32_t kids[4] = {left[f.bin], right[f.bin], 0u, 0u};
+  uint32_t kids[4] = {src.left(f.bin), src.right(f.bin), 0u, 0u};
   uint32_t nk = 2;
   while (nk < 4) {
     int best = -1;
     double best_area = -1.0;
     for (uint32_t k = 0; k < nk; k++) {
       const uint32_t c = kids[k];
-      if ((c & BIN_LEAF) || bin_count(c, first, last) <= max_leaf) continue;  // leaves are not opened
-      const double a = area(node_boxes[c]);
+      if (src.is_leaf(c)) continue;  // leaves are not opened
+      const double a = area(src.box(c));
       if (a > best_area) {
         best_area = a;
         best = (int)k;
@@ -225,8 +285,8 @@ __global__ void collapse_kernel(const Frontier* __restrict__ cur, uint32_t n_cur
     }
     if (best < 0) break;
     const uint32_t open = kids[best];
-    kids[best] = left[open];
-    kids[nk++] = right[open];
+    kids[best] = src.left(open);
+    kids[nk++] = src.right(open);
   }
   Box6 kb[4];
   Box6 nb;
@@ -235,17 +295,12 @@ __global__ void collapse_kernel(const Frontier* __restrict__ cur, uint32_t n_cur
     nb.hi[a] = -__builtin_huge_val();
   }
   for (uint32_t k = 0; k < nk; k++) {
-    const uint32_t c = kids[k];
-    kb[k] = (c & BIN_LEAF) ? leaf_boxes[order[c & ~BIN_LEAF]] : node_boxes[c];
-    for (int a = 0; a < 3; a++) {
-      nb.lo[a] = fmin(nb.lo[a], kb[k].lo[a]);
-      nb.hi[a] = fmax(nb.hi[a], kb[k].hi[a]);
-    }
+    kb[k] = src.box(kids[k]);
+    nb = box_union(nb, kb[k]);
   }
   // child boxes in the node format: f32 rounded outward, or quantized in the node's frame (rp_layout.h
   // qframe; rp_bvh.cpp node_frame / Collapser)
-  typedef typename std::conditional<NF == rpl::NODES_Q8, rpl::Node4Q, rpl::Node4>::type NodeT;
-  NodeT nd;
+  NodeOf<NF> nd;
   if constexpr (NF == rpl::NODES_Q8) {
     for (int a = 0; a < 3; a++) {
       const bool ok = isfinite(nb.lo[a]) && isfinite(nb.hi[a]) && nb.lo[a] <= nb.hi[a];
@@ -256,8 +311,9 @@ __global__ void collapse_kernel(const Frontier* __restrict__ cur, uint32_t n_cur
   }
   // the inner children's wide nodes are allocated as one consecutive family (rp_bvh.cpp Collapser)
   uint32_t n_inner = 0;
-  for (uint32_t k = 0; k < nk; k++) n_inner += bin_count(kids[k], first, last) > max_leaf;
+  for (uint32_t k = 0; k < nk; k++) n_inner += !src.is_leaf(kids[k]);
   uint32_t fam = n_inner ? atomicAdd(&counters[0], n_inner) : 0u;
+  uint32_t off = f.poff;
   for (uint32_t k = 0; k < 4; k++) {
     if (k >= nk) {
       if constexpr (NF == rpl::NODES_Q8) rpl::empty_child(nd, (int)k);
@@ -268,18 +324,18 @@ __global__ void collapse_kernel(const Frontier* __restrict__ cur, uint32_t n_cur
     const uint32_t c = kids[k];
     if constexpr (NF == rpl::NODES_Q8) rpl::quantize_child(nd, (int)k, kb[k].lo, kb[k].hi);
     else rpl::f32_child(nd, (int)k, kb[k].lo, kb[k].hi);
-    const uint32_t cnt = bin_count(c, first, last);
-    if (cnt <= max_leaf) {
-      const uint32_t lo = (c & BIN_LEAF) ? (c & ~BIN_LEAF) : first[c];
-      nd.child[k] = rpl::ENTRY_LEAF | ((cnt - 1u) << rpl::LEAF_SHIFT) | lo;
+    const uint32_t cnt = src.count(c);
+    if (src.is_leaf(c)) {
+      nd.child[k] = rpl::ENTRY_LEAF | ((cnt - 1u) << rpl::LEAF_SHIFT) | src.place_leaf(c, off);
       atomicAdd(&counters[2], 1u);
     } else {
       const uint32_t w = fam++;
       nd.child[k] = w;
-      next[atomicAdd(&counters[1], 1u)] = Frontier{c, w};
+      next[atomicAdd(&counters[1], 1u)] = Frontier{c, w, off};
     }
+    off += cnt;
   }
-  reinterpret_cast<NodeT*>(nodes)[f.wide] = nd;
+  reinterpret_cast<NodeOf<NF>*>(nodes)[f.wide] = nd;
 }
 
 __global__ void permute_kernel(uint32_t n, const uint32_t* __restrict__ order, const rpl::Prim* __restrict__ prims_in,
@@ -297,7 +353,11 @@ __global__ void order_kernel(uint32_t n, const uint64_t* __restrict__ keys, uint
   if (k < n) order[k] = (uint32_t)keys[k];
 }
 
-unsigned grid(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
+// kernel k over n threads, in blocks of B on the null stream
+template <unsigned B = 256, class K, class... A>
+void launch(K k, uint64_t n, A... a) {
+  hipLaunchKernelGGL(k, dim3((unsigned)((n + B - 1) / B)), dim3(B), 0, nullptr, a...);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Depth-first layout of a collapsed wide tree.  The level-by-level collapse numbers wide nodes by atomic family
@@ -311,8 +371,7 @@ unsigned grid(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / 
 // pad slots are zero and never referenced), 1 packs the families.
 template <uint32_t NF>
 __device__ __forceinline__ const uint32_t* node_children(const void* nodes, uint32_t i) {
-  typedef typename std::conditional<NF == rpl::NODES_Q8, rpl::Node4Q, rpl::Node4>::type NodeT;
-  return reinterpret_cast<const NodeT*>(nodes)[i].child;
+  return reinterpret_cast<const NodeOf<NF>*>(nodes)[i].child;
 }
 
 __global__ void record_level_kernel(const uint32_t* __restrict__ wide_of, uint32_t stride_words, uint32_t n,
@@ -360,77 +419,114 @@ __global__ void dfs_index_kernel(const uint32_t* __restrict__ ids, uint32_t n, c
 template <uint32_t NF>
 __global__ void relayout_kernel(uint32_t n, const void* __restrict__ nodes, const uint32_t* __restrict__ newid,
                                 void* __restrict__ out) {
-  typedef typename std::conditional<NF == rpl::NODES_Q8, rpl::Node4Q, rpl::Node4>::type NodeT;
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= n) return;
-  NodeT nd = reinterpret_cast<const NodeT*>(nodes)[u];
+  NodeOf<NF> nd = reinterpret_cast<const NodeOf<NF>*>(nodes)[u];
   for (int k = 0; k < 4; k++)
     if (!(nd.child[k] & rpl::ENTRY_LEAF)) nd.child[k] = newid[nd.child[k]];
-  reinterpret_cast<NodeT*>(out)[newid[u]] = nd;
+  reinterpret_cast<NodeOf<NF>*>(out)[newid[u]] = nd;
 }
 
-// Renumber the n_nodes wide nodes of `nodes` depth-first (see above); `level_ids` holds each collapse level's wide
-// node ids (level k at level_off[k] .. level_off[k + 1]).  Replaces *nodes (the old buffer is freed).
-int dfs_relayout(void** nodes, uint32_t node_format, uint64_t* n_nodes_io, const uint32_t* level_ids,
-                 const std::vector<uint32_t>& level_off, uint32_t align, std::string& err) {
-  const uint64_t n_nodes = *n_nodes_io;
+// Every collapse level's wide node ids: level k at ids[off[k] .. off[k + 1]).
+struct Levels {
+  DevBuf<uint32_t> ids;
+  std::vector<uint32_t> off{0};
+};
+
+// Renumber the n_nodes wide nodes of `nodes` depth-first (see above).  Replaces `nodes` and n_nodes.
+int dfs_relayout(DevBuf<uint8_t>& nodes, uint32_t node_format, uint64_t& n_nodes, const Levels& lv, uint32_t align,
+                 std::string& err) {
   const size_t nb = node_format == rpl::NODES_Q8 ? sizeof(rpl::Node4Q) : sizeof(rpl::Node4);
-  uint32_t *below = nullptr, *newid = nullptr, *fam = nullptr;
-  void* out = nullptr;
-  hipError_t e = hipMalloc((void**)&below, sizeof(uint32_t) * n_nodes);
-  if (e == hipSuccess) e = hipMalloc((void**)&newid, sizeof(uint32_t) * n_nodes);
-  if (e == hipSuccess) e = hipMalloc((void**)&fam, sizeof(uint32_t) * n_nodes);
-  const unsigned B = 256;
-  const uint32_t L = (uint32_t)level_off.size() - 1;
-  for (uint32_t k = L; k-- > 0 && e == hipSuccess;) {
-    const uint32_t n = level_off[k + 1] - level_off[k];
-    if (node_format == rpl::NODES_Q8)
-      hipLaunchKernelGGL(subtree_count_kernel<rpl::NODES_Q8>, dim3(grid(n, B)), dim3(B), 0, nullptr, level_ids + level_off[k],
-                         n, *nodes, align, below);
-    else
-      hipLaunchKernelGGL(subtree_count_kernel<rpl::NODES_F32>, dim3(grid(n, B)), dim3(B), 0, nullptr, level_ids + level_off[k],
-                         n, *nodes, align, below);
-    e = hipGetLastError();
+  const uint32_t L = (uint32_t)lv.off.size() - 1;
+  const uint32_t* ids = lv.ids.get();
+  DevBuf<uint32_t> below, newid, fam;
+  DevBuf<uint8_t> out;
+  hipError_t e = hipSuccess;
+  alloc(e, below, n_nodes);
+  alloc(e, newid, n_nodes);
+  alloc(e, fam, n_nodes);
+  RPG_CHECK("depth-first relayout");
+  for (uint32_t k = L; k-- > 0;) {
+    const uint32_t n = lv.off[k + 1] - lv.off[k];
+    with_format(node_format, [&](auto nf) {
+      launch(subtree_count_kernel<decltype(nf)::value>, n, ids + lv.off[k], n, nodes.get(), align, below.get());
+    });
+    RPG_CHECK("depth-first relayout");
   }
   const uint32_t root_new = 0, root_fam = align;  // the root, padded to the alignment, then its family
   uint32_t root = 0, below_root = 0;
-  if (e == hipSuccess) e = hipMemcpy(&root, level_ids, sizeof root, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&below_root, below + root, sizeof below_root, hipMemcpyDeviceToHost);
+  e = hipMemcpy(&root, ids, sizeof root, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(&below_root, below.get() + root, sizeof below_root, hipMemcpyDeviceToHost);
   const uint64_t total = (uint64_t)root_fam + below_root;  // == n_nodes when align == 1
-  if (e == hipSuccess) e = hipMalloc(&out, nb * total);
-  if (e == hipSuccess && total != n_nodes) e = hipMemset(out, 0, nb * total);
-  if (e == hipSuccess) e = hipMemcpy(newid + root, &root_new, sizeof root_new, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(fam + root, &root_fam, sizeof root_fam, hipMemcpyHostToDevice);
-  for (uint32_t k = 0; k < L && e == hipSuccess; k++) {
-    const uint32_t n = level_off[k + 1] - level_off[k];
-    if (node_format == rpl::NODES_Q8)
-      hipLaunchKernelGGL(dfs_index_kernel<rpl::NODES_Q8>, dim3(grid(n, B)), dim3(B), 0, nullptr, level_ids + level_off[k], n,
-                         *nodes, below, align, newid, fam);
-    else
-      hipLaunchKernelGGL(dfs_index_kernel<rpl::NODES_F32>, dim3(grid(n, B)), dim3(B), 0, nullptr, level_ids + level_off[k], n,
-                         *nodes, below, align, newid, fam);
-    e = hipGetLastError();
+  alloc(e, out, nb * total);
+  if (e == hipSuccess && total != n_nodes) e = hipMemset(out.get(), 0, nb * total);
+  if (e == hipSuccess) e = hipMemcpy(newid.get() + root, &root_new, sizeof root_new, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(fam.get() + root, &root_fam, sizeof root_fam, hipMemcpyHostToDevice);
+  RPG_CHECK("depth-first relayout");
+  for (uint32_t k = 0; k < L; k++) {
+    const uint32_t n = lv.off[k + 1] - lv.off[k];
+    with_format(node_format, [&](auto nf) {
+      launch(dfs_index_kernel<decltype(nf)::value>, n, ids + lv.off[k], n, nodes.get(), below.get(), align, newid.get(),
+             fam.get());
+    });
+    RPG_CHECK("depth-first relayout");
   }
-  if (e == hipSuccess) {
-    if (node_format == rpl::NODES_Q8)
-      hipLaunchKernelGGL(relayout_kernel<rpl::NODES_Q8>, dim3(grid(n_nodes, B)), dim3(B), 0, nullptr, (uint32_t)n_nodes, *nodes,
-                         newid, out);
-    else
-      hipLaunchKernelGGL(relayout_kernel<rpl::NODES_F32>, dim3(grid(n_nodes, B)), dim3(B), 0, nullptr, (uint32_t)n_nodes, *nodes,
-                         newid, out);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  for (void* p : {(void*)below, (void*)newid, (void*)fam}) if (p) (void)hipFree(p);
-  if (e != hipSuccess) {
-    if (out) (void)hipFree(out);
-    err = std::string("depth-first relayout: ") + hipGetErrorString(e);
-    return RP_EHIP;
-  }
-  (void)hipFree(*nodes);
-  *nodes = out;
-  *n_nodes_io = total;
+  with_format(node_format, [&](auto nf) {
+    launch(relayout_kernel<decltype(nf)::value>, n_nodes, (uint32_t)n_nodes, nodes.get(), newid.get(), out.get());
+  });
+  RPG_CHECK("depth-first relayout");
+  e = hipDeviceSynchronize();
+  RPG_CHECK("depth-first relayout");
+  nodes = std::move(out);  // the old buffer goes with `out`
+  n_nodes = total;
   return RP_OK;
+}
+
+// The collapse of either binary tree, level by level from its root (-> wide node 0, primitives from slot 0) into
+// `nodes`; fills out.n_nodes / n_leaves / max_depth.  `rec`: every level's wide node ids, for the depth-first relayout.
+template <class Src>
+int collapse_levels(const Src& src, uint32_t root, uint32_t n, uint32_t node_format, void* nodes, GpuTree& out, Levels* rec,
+                    std::string& err) {
+  DevBuf<Frontier> fa, fb;
+  DevBuf<uint32_t> ctr;
+  hipError_t e = hipSuccess;
+  alloc(e, fa, n);
+  alloc(e, fb, n);
+  alloc(e, ctr, 4);
+  if (rec) alloc(e, rec->ids, n);
+  if (e != hipSuccess) return alloc_failed(Src::build, e, err);
+  const Frontier first{root, 0u, 0u};
+  const uint32_t ctr0[4] = {1u, 0u, 0u, 0u};  // wide node 0 taken
+  e = hipMemcpy(fa.get(), &first, sizeof first, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ctr.get(), ctr0, sizeof ctr0, hipMemcpyHostToDevice);
+  RPG_CHECK(std::string(Src::stage) + " setup");
+  uint32_t n_cur = 1, depth = 0;
+  for (;;) {
+    e = hipMemset(ctr.get() + 1, 0, sizeof(uint32_t));
+    RPG_CHECK(Src::stage);
+    if (rec) {
+      launch(record_level_kernel, n_cur, &fa.get()->wide, (uint32_t)(sizeof(Frontier) / 4), n_cur,
+             rec->ids.get() + rec->off.back());
+      rec->off.push_back(rec->off.back() + n_cur);
+    }
+    with_format(node_format, [&](auto nf) {
+      launch(collapse_kernel<decltype(nf)::value, Src>, n_cur, src, fa.get(), n_cur, fb.get(), ctr.get(), nodes);
+    });
+    RPG_CHECK(Src::stage);
+    uint32_t c[4];
+    e = hipMemcpy(c, ctr.get(), sizeof c, hipMemcpyDeviceToHost);
+    RPG_CHECK(Src::stage);
+    if (c[0] > n) return failed(err, RP_EINTERNAL, std::string(Src::build) + ": wide node overflow");
+    if (c[1] == 0) {
+      out.n_nodes = c[0];
+      out.n_leaves = c[2];
+      out.max_depth = depth;
+      return RP_OK;
+    }
+    depth++;
+    n_cur = c[1];
+    std::swap(fa, fb);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -451,15 +547,6 @@ struct PNode {
   uint32_t left, right, size, leaf;  // children (BIN_LEAF | primitive, or a node id); primitives below; 1 = the
                                      // subtree becomes one leaf of the wide tree (the SAH decision, ploc_apply)
 };
-
-__device__ __forceinline__ Box6 box_union(const Box6& a, const Box6& b) {
-  Box6 u;
-  for (int c = 0; c < 3; c++) {
-    u.lo[c] = fmin(a.lo[c], b.lo[c]);
-    u.hi[c] = fmax(a.hi[c], b.hi[c]);
-  }
-  return u;
-}
 
 __global__ void ploc_init_kernel(uint32_t n, const uint32_t* __restrict__ order, const Box6* __restrict__ boxes,
                                  uint32_t* __restrict__ ref, Box6* __restrict__ cbox, uint32_t* __restrict__ csize,
@@ -555,409 +642,223 @@ __global__ void ploc_apply_kernel(uint32_t m, const uint32_t* __restrict__ nn, c
   }
 }
 
-struct PFront {
-  uint32_t bin, wide, poff;  // binary node, its wide node, the first primitive slot of its subtree
+// The PLOC tree as collapse_kernel's source: a leaf is where the SAH said so, and the primitives are laid out
+// depth-first as the frontier descends -- each child subtree takes the next run of primitive slots, and a leaf child
+// writes its primitives' ids into perm there.
+struct PlocSrc {
+  static constexpr const char* stage = "PLOC collapse";
+  static constexpr const char* build = "PLOC build";
+  const PNode* __restrict__ nodes;
+  const Box6 *__restrict__ prim_boxes, *__restrict__ nbox;
+  uint32_t* __restrict__ perm;
+  __device__ uint32_t left(uint32_t c) const { return nodes[c].left; }
+  __device__ uint32_t right(uint32_t c) const { return nodes[c].right; }
+  __device__ uint32_t count(uint32_t c) const { return (c & BIN_LEAF) ? 1u : nodes[c].size; }
+  __device__ bool is_leaf(uint32_t c) const { return (c & BIN_LEAF) || nodes[c].leaf; }
+  __device__ Box6 box(uint32_t c) const { return (c & BIN_LEAF) ? prim_boxes[c & ~BIN_LEAF] : nbox[c]; }
+  // the subtree's primitives (<= max_leaf <= 8: a binary subtree of <= 7 inner nodes) into perm[off ...]
+  __device__ uint32_t place_leaf(uint32_t c, uint32_t off) const {
+    uint32_t stk[8], sp = 0, w = off;
+    stk[sp++] = c;
+    while (sp) {
+      const uint32_t x = stk[--sp];
+      if (x & BIN_LEAF) {
+        perm[w++] = x & ~BIN_LEAF;
+      } else {
+        stk[sp++] = nodes[x].right;
+        stk[sp++] = nodes[x].left;
+      }
+    }
+    return off;
+  }
 };
 
-__device__ __forceinline__ uint32_t psize(uint32_t c, const PNode* nodes) { return (c & BIN_LEAF) ? 1u : nodes[c].size; }
-__device__ __forceinline__ bool pleaf(uint32_t c, const PNode* nodes) { return (c & BIN_LEAF) || nodes[c].leaf; }
 
-// One level of the collapse of the PLOC tree (collapse_kernel's rule: open the inner child of largest area until four
-// children); primitives are laid out depth-first as the frontier descends: each child subtree takes the next run of
-// primitive slots, and a leaf child (<= max_leaf primitives) writes its primitives' ids into perm there.
-template <uint32_t NF>
-__global__ void ploc_collapse_kernel(const PFront* __restrict__ cur, uint32_t n_cur, PFront* __restrict__ next,
-                                     uint32_t* __restrict__ counters /* [0] wide nodes, [1] next frontier, [2] leaves */,
-                                     uint32_t max_leaf, const Box6* __restrict__ prim_boxes,
-                                     const PNode* __restrict__ bnodes, const Box6* __restrict__ nbox,
-                                     uint32_t* __restrict__ perm, void* __restrict__ nodes) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n_cur) return;
-  const PFront f = cur[t];
-  uint32_t kids[4] = {bnodes[f.bin].left, bnodes[f.bin].right, 0u, 0u};
-  uint32_t nk = 2;
-  while (nk < 4) {
-    int best = -1;
-    double best_area = -1.0;
-    for (uint32_t k = 0; k < nk; k++) {
-      const uint32_t c = kids[k];
-      if (pleaf(c, bnodes)) continue;
-      const double a = area(nbox[c]);
-      if (a > best_area) {
-        best_area = a;
-        best = (int)k;
-      }
-    }
-    if (best < 0) break;
-    const uint32_t open = kids[best];
-    kids[best] = bnodes[open].left;
-    kids[nk++] = bnodes[open].right;
-  }
-  Box6 kb[4];
-  Box6 nb;
-  for (int a = 0; a < 3; a++) {
-    nb.lo[a] = __builtin_huge_val();
-    nb.hi[a] = -__builtin_huge_val();
-  }
-  for (uint32_t k = 0; k < nk; k++) {
-    const uint32_t c = kids[k];
-    kb[k] = (c & BIN_LEAF) ? prim_boxes[c & ~BIN_LEAF] : nbox[c];
-    nb = box_union(nb, kb[k]);
-  }
-  typedef typename std::conditional<NF == rpl::NODES_Q8, rpl::Node4Q, rpl::Node4>::type NodeT;
-  NodeT nd;
-  if constexpr (NF == rpl::NODES_Q8) {
-    for (int a = 0; a < 3; a++) {
-      const bool ok = isfinite(nb.lo[a]) && isfinite(nb.hi[a]) && nb.lo[a] <= nb.hi[a];
-      rpl::qframe(ok ? nb.lo[a] : 0.0, ok ? nb.hi[a] : 0.0, nd.o[a], nd.s[a]);
-    }
-  } else {
-    for (int k = 0; k < 4; k++) nd.pad[k] = 0;
-  }
-  uint32_t n_inner = 0;
-  for (uint32_t k = 0; k < nk; k++) n_inner += !pleaf(kids[k], bnodes);
-  uint32_t fam = n_inner ? atomicAdd(&counters[0], n_inner) : 0u;
-  uint32_t off = f.poff;
-  for (uint32_t k = 0; k < 4; k++) {
-    if (k >= nk) {
-      if constexpr (NF == rpl::NODES_Q8) rpl::empty_child(nd, (int)k);
-      else rpl::f32_empty(nd, (int)k);
-      nd.child[k] = rpl::ENTRY_EMPTY;
-      continue;
-    }
-    const uint32_t c = kids[k];
-    if constexpr (NF == rpl::NODES_Q8) rpl::quantize_child(nd, (int)k, kb[k].lo, kb[k].hi);
-    else rpl::f32_child(nd, (int)k, kb[k].lo, kb[k].hi);
-    const uint32_t cnt = psize(c, bnodes);
-    if (pleaf(c, bnodes)) {
-      nd.child[k] = rpl::ENTRY_LEAF | ((cnt - 1u) << rpl::LEAF_SHIFT) | off;
-      // the subtree's primitives (<= max_leaf <= 8: a binary subtree of <= 7 inner nodes) into perm[off ...]
-      uint32_t stk[8], sp = 0, w = off;
-      stk[sp++] = c;
-      while (sp) {
-        const uint32_t x = stk[--sp];
-        if (x & BIN_LEAF) {
-          perm[w++] = x & ~BIN_LEAF;
-        } else {
-          stk[sp++] = bnodes[x].right;
-          stk[sp++] = bnodes[x].left;
-        }
-      }
-      atomicAdd(&counters[2], 1u);
-    } else {
-      const uint32_t wn = fam++;
-      nd.child[k] = wn;
-      next[atomicAdd(&counters[1], 1u)] = PFront{c, wn, off};
-    }
-    off += cnt;
-  }
-  reinterpret_cast<NodeT*>(nodes)[f.wide] = nd;
+// What the common prologue leaves on the device: the input in hittable order and its Morton order.
+struct Sorted {
+  uint32_t n = 0;
+  DevBuf<Box6> boxes;
+  DevBuf<rpl::Prim> prims;
+  DevBuf<rpl::PrimRef> refs;
+  DevBuf<uint64_t> keys;   // sorted (the LBVH's radix tree reads them)
+  DevBuf<uint32_t> order;  // order[k]: the primitive at sorted position k
+};
+
+// The three outputs, owned here until the build has succeeded.
+struct Outputs {
+  DevBuf<uint8_t> nodes;  // at most n - 1 wide nodes (each inner wide node has >= 2 children)
+  DevBuf<rpl::Prim> prims;
+  DevBuf<rpl::PrimRef> refs;
+};
+
+// The builds' last step: the primitive records into leaf order, and the wait for everything queued.
+int permute(const Sorted& s, const uint32_t* order, Outputs& o, const char* what, const char* build, std::string& err) {
+  hipError_t e = hipSuccess;
+  launch(permute_kernel, s.n, s.n, order, s.prims.get(), s.refs.get(), o.prims.get(), o.refs.get());
+  RPG_CHECK(what);
+  e = hipDeviceSynchronize();
+  RPG_CHECK(build);
+  return RP_OK;
 }
 
-}  // namespace
-
-namespace {
-
-// PLOC build (see the kernels above) from the Morton-sorted keys, then the depth-first collapse; fills out.d_nodes
-// and out.d_prims / d_prim_refs (permuted).  Device buffers: boxes / prims_in / refs_in in hittable order.
-int build_ploc(uint32_t n, const uint32_t* d_order, const Box6* d_boxes, const rpl::Prim* d_prims_in,
-               const rpl::PrimRef* d_refs_in, uint32_t max_leaf, double cost_traverse, uint32_t node_format, uint32_t align,
-               GpuTree& out, std::string& err) {
-  std::vector<void*> tmp;
+// LBVH: the radix tree over the sorted keys, its boxes bottom-up, the collapse; the sorted order is the leaf order.
+int build_lbvh(const Sorted& s, uint32_t max_leaf, uint32_t node_format, Outputs& o, GpuTree& out, std::string& err) {
+  const uint32_t n = s.n;
+  DevBuf<uint32_t> left, right, pin, pleaf, first, last, visits;
+  DevBuf<Box6> nboxes;
   hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (e != hipSuccess) return;
-    e = hipMalloc(p, bytes);
-    if (e == hipSuccess) tmp.push_back(*p);
-    else *p = nullptr;
-  };
-  uint32_t *ref[2] = {nullptr, nullptr}, *csz[2] = {nullptr, nullptr};
-  Box6* cbox[2] = {nullptr, nullptr};
-  double* ccost[2] = {nullptr, nullptr};
-  uint32_t *d_nn = nullptr, *d_keep = nullptr, *d_kpos = nullptr, *d_merge = nullptr, *d_mrank = nullptr;
-  uint32_t *d_perm = nullptr, *d_ctr = nullptr;
-  PNode* d_bn = nullptr;
-  Box6* d_nbox = nullptr;
-  PFront *d_fa = nullptr, *d_fb = nullptr;
+  for (DevBuf<uint32_t>* b : {&left, &right, &pin, &pleaf, &first, &last, &visits}) alloc(e, *b, n);
+  alloc(e, nboxes, n);
+  if (e != hipSuccess) return alloc_failed(RadixSrc::build, e, err);
+  e = hipMemset(visits.get(), 0, sizeof(uint32_t) * n);
+  RPG_CHECK("upload (device BVH build)");
+  launch(radix_tree_kernel, n - 1, n, s.keys.get(), left.get(), right.get(), pin.get(), pleaf.get(), first.get(),
+         last.get());
+  RPG_CHECK("radix tree");
+  launch(boxes_kernel, n, n, s.boxes.get(), s.order.get(), left.get(), right.get(), pin.get(), pleaf.get(),
+         nboxes.get(), visits.get());
+  RPG_CHECK("boxes");
+  const RadixSrc src{left.get(), right.get(), first.get(), last.get(), s.order.get(), s.boxes.get(), nboxes.get(), max_leaf};
+  if (const int rc = collapse_levels(src, 0u, n, node_format, o.nodes.get(), out, nullptr, err)) return rc;
+  return permute(s, s.order.get(), o, "permute", RadixSrc::build, err);
+}
+
+// PLOC (see the kernels above) over the Morton order, the collapse with the primitives laid out depth-first (perm), and
+// the depth-first relayout of the nodes.
+int build_ploc(const Sorted& s, uint32_t max_leaf, double cost_traverse, uint32_t node_format, uint32_t align, Outputs& o,
+               GpuTree& out, std::string& err) {
+  const uint32_t n = s.n;
+  DevBuf<uint32_t> ref[2], csz[2], nn, keep, kpos, merge, mrank, perm;
+  DevBuf<Box6> cbox[2], nbox;
+  DevBuf<double> ccost[2];
+  DevBuf<PNode> bn;
+  DevBuf<uint8_t> scan;
+  hipError_t e = hipSuccess;
   for (int b = 0; b < 2; b++) {
-    alloc((void**)&ref[b], sizeof(uint32_t) * n);
-    alloc((void**)&csz[b], sizeof(uint32_t) * n);
-    alloc((void**)&cbox[b], sizeof(Box6) * n);
-    alloc((void**)&ccost[b], sizeof(double) * n);
+    alloc(e, ref[b], n);
+    alloc(e, csz[b], n);
+    alloc(e, cbox[b], n);
+    alloc(e, ccost[b], n);
   }
-  alloc((void**)&d_nn, sizeof(uint32_t) * n);
-  alloc((void**)&d_keep, sizeof(uint32_t) * n);
-  alloc((void**)&d_kpos, sizeof(uint32_t) * n);
-  alloc((void**)&d_merge, sizeof(uint32_t) * n);
-  alloc((void**)&d_mrank, sizeof(uint32_t) * n);
-  alloc((void**)&d_perm, sizeof(uint32_t) * n);
-  alloc((void**)&d_ctr, sizeof(uint32_t) * 4);
-  alloc((void**)&d_bn, sizeof(PNode) * n);
-  alloc((void**)&d_nbox, sizeof(Box6) * n);
-  alloc((void**)&d_fa, sizeof(PFront) * n);
-  alloc((void**)&d_fb, sizeof(PFront) * n);
+  for (DevBuf<uint32_t>* b : {&nn, &keep, &kpos, &merge, &mrank, &perm}) alloc(e, *b, n);
+  alloc(e, bn, n);
+  alloc(e, nbox, n);
   size_t scan_bytes = 0;
-  void* d_scan = nullptr;
-  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_keep, d_kpos, (int)n);
-  alloc(&d_scan, scan_bytes);
-  auto done = [&](int code, const std::string& msg) {
-    for (void* p : tmp) (void)hipFree(p);
-    if (code != RP_OK) err = msg;
-    return code;
-  };
-  if (e != hipSuccess) return done(RP_ENOMEM, std::string("hipMalloc (PLOC build): ") + hipGetErrorString(e));
-#define RPG_CHECK2(what)                                                                         \
-  do {                                                                                           \
-    if (e == hipSuccess) e = hipGetLastError();                                                  \
-    if (e != hipSuccess) return done(RP_EHIP, std::string(what) + ": " + hipGetErrorString(e));  \
-  } while (0)
-  const unsigned B = 256;
-  hipLaunchKernelGGL(ploc_init_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_order, d_boxes, ref[0], cbox[0],
-                     csz[0], ccost[0]);
-  RPG_CHECK2("PLOC init");
+  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep.get(), kpos.get(), (int)n);
+  alloc(e, scan, scan_bytes);
+  if (e != hipSuccess) return alloc_failed(PlocSrc::build, e, err);
+  launch(ploc_init_kernel, n, n, s.order.get(), s.boxes.get(), ref[0].get(), cbox[0].get(), csz[0].get(),
+         ccost[0].get());
+  RPG_CHECK("PLOC init");
   uint32_t m = n, node_base = 0;
   int cb = 0;
   while (m > 1) {
-    hipLaunchKernelGGL(ploc_nn_kernel, dim3(grid(m, PLOC_B)), dim3(PLOC_B), 0, nullptr, m, cbox[cb], d_nn);
-    hipLaunchKernelGGL(ploc_flags_kernel, dim3(grid(m, B)), dim3(B), 0, nullptr, m, d_nn, d_keep, d_merge);
-    RPG_CHECK2("PLOC neighbours");
-    e = hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_keep, d_kpos, (int)m);
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_merge, d_mrank, (int)m);
+    launch<PLOC_B>(ploc_nn_kernel, m, m, cbox[cb].get(), nn.get());
+    launch(ploc_flags_kernel, m, m, nn.get(), keep.get(), merge.get());
+    RPG_CHECK("PLOC neighbours");
+    e = hipcub::DeviceScan::ExclusiveSum(scan.get(), scan_bytes, keep.get(), kpos.get(), (int)m);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(scan.get(), scan_bytes, merge.get(), mrank.get(), (int)m);
     uint32_t last[4];
-    if (e == hipSuccess) e = hipMemcpy(&last[0], d_kpos + (m - 1), 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&last[1], d_keep + (m - 1), 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&last[2], d_mrank + (m - 1), 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(&last[3], d_merge + (m - 1), 4, hipMemcpyDeviceToHost);
-    RPG_CHECK2("PLOC scan");
+    if (e == hipSuccess) e = hipMemcpy(&last[0], kpos.get() + (m - 1), 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&last[1], keep.get() + (m - 1), 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&last[2], mrank.get() + (m - 1), 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&last[3], merge.get() + (m - 1), 4, hipMemcpyDeviceToHost);
+    RPG_CHECK("PLOC scan");
     const uint32_t m2 = last[0] + last[1], merges = last[2] + last[3];
-    if (merges == 0 || m2 != m - merges) return done(RP_EINTERNAL, "PLOC build: no progress");
-    hipLaunchKernelGGL(ploc_apply_kernel, dim3(grid(m, B)), dim3(B), 0, nullptr, m, d_nn, d_keep, d_kpos, d_merge, d_mrank,
-                       node_base, ref[cb], cbox[cb], csz[cb], ccost[cb], ref[1 - cb], cbox[1 - cb], csz[1 - cb],
-                       ccost[1 - cb], d_bn, d_nbox, max_leaf, cost_traverse);
-    RPG_CHECK2("PLOC merge");
+    if (merges == 0 || m2 != m - merges) return failed(err, RP_EINTERNAL, "PLOC build: no progress");
+    launch(ploc_apply_kernel, m, m, nn.get(), keep.get(), kpos.get(), merge.get(), mrank.get(), node_base,
+           ref[cb].get(), cbox[cb].get(), csz[cb].get(), ccost[cb].get(), ref[1 - cb].get(), cbox[1 - cb].get(),
+           csz[1 - cb].get(), ccost[1 - cb].get(), bn.get(), nbox.get(), max_leaf, cost_traverse);
+    RPG_CHECK("PLOC merge");
     node_base += merges;
     m = m2;
     cb = 1 - cb;
   }
-  if (node_base != n - 1) return done(RP_EINTERNAL, "PLOC build: node count");
-  uint32_t* d_levels = nullptr;  // every collapse level's wide node ids (the depth-first relayout)
-  alloc((void**)&d_levels, sizeof(uint32_t) * n);
-  if (e != hipSuccess) return done(RP_ENOMEM, std::string("hipMalloc (PLOC build): ") + hipGetErrorString(e));
-  std::vector<uint32_t> level_off{0};
-  // collapse from the root (the last node made) into wide node 0, primitives from slot 0
-  const PFront root{n - 2, 0u, 0u};
-  const uint32_t ctr0[4] = {1u, 0u, 0u, 0u};
-  e = hipMemcpy(d_fa, &root, sizeof root, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ctr, ctr0, sizeof ctr0, hipMemcpyHostToDevice);
-  RPG_CHECK2("PLOC collapse setup");
-  uint32_t n_cur = 1, depth = 0;
-  for (;;) {
-    e = hipMemset(d_ctr + 1, 0, sizeof(uint32_t));
-    RPG_CHECK2("PLOC collapse");
-    hipLaunchKernelGGL(record_level_kernel, dim3(grid(n_cur, B)), dim3(B), 0, nullptr, &d_fa->wide,
-                       (uint32_t)(sizeof(PFront) / 4), n_cur, d_levels + level_off.back());
-    level_off.push_back(level_off.back() + n_cur);
-    if (node_format == rpl::NODES_Q8)
-      hipLaunchKernelGGL(ploc_collapse_kernel<rpl::NODES_Q8>, dim3(grid(n_cur, B)), dim3(B), 0, nullptr, d_fa, n_cur, d_fb,
-                         d_ctr, max_leaf, d_boxes, d_bn, d_nbox, d_perm, out.d_nodes);
-    else
-      hipLaunchKernelGGL(ploc_collapse_kernel<rpl::NODES_F32>, dim3(grid(n_cur, B)), dim3(B), 0, nullptr, d_fa, n_cur, d_fb,
-                         d_ctr, max_leaf, d_boxes, d_bn, d_nbox, d_perm, out.d_nodes);
-    RPG_CHECK2("PLOC collapse");
-    uint32_t ctr[4];
-    e = hipMemcpy(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost);
-    RPG_CHECK2("PLOC collapse");
-    if (ctr[0] > n) return done(RP_EINTERNAL, "PLOC build: wide node overflow");
-    if (ctr[1] == 0) {
-      out.n_nodes = ctr[0];
-      out.n_leaves = ctr[2];
-      break;
-    }
-    depth++;
-    n_cur = ctr[1];
-    std::swap(d_fa, d_fb);
-  }
-  out.max_depth = depth;
-  {
-    std::string rerr;
-    const int rc = dfs_relayout(&out.d_nodes, node_format, &out.n_nodes, d_levels, level_off, align, rerr);
-    if (rc) return done(rc, rerr);
-  }
-  hipLaunchKernelGGL(permute_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_perm, d_prims_in, d_refs_in, out.d_prims,
-                     out.d_prim_refs);
-  RPG_CHECK2("PLOC permute");
-  e = hipDeviceSynchronize();
-  RPG_CHECK2("PLOC build");
-#undef RPG_CHECK2
-  return done(RP_OK, "");
+  if (node_base != n - 1) return failed(err, RP_EINTERNAL, "PLOC build: node count");
+  Levels levels;
+  const PlocSrc src{bn.get(), s.boxes.get(), nbox.get(), perm.get()};
+  // the root is the last node made
+  if (const int rc = collapse_levels(src, n - 2, n, node_format, o.nodes.get(), out, &levels, err)) return rc;
+  if (const int rc = dfs_relayout(o.nodes, node_format, out.n_nodes, levels, align, err)) return rc;
+  return permute(s, perm.get(), o, "PLOC permute", PlocSrc::build, err);
 }
 
 }  // namespace
 
-// Temporaries are freed on every path; on success the caller owns out.d_nodes / d_prims / d_prim_refs.
+// On success the caller owns out.d_nodes / d_prims / d_prim_refs; on failure `out` is empty.
 int build_gpu(const rpb::PrimInput& in, uint32_t max_leaf, uint32_t node_format, uint32_t algo, double cost_traverse,
               uint32_t align, GpuTree& out, std::string& err) {
   out = GpuTree{};
   const uint32_t n = (uint32_t)in.prims.size();
-  if (n < 2) {
-    err = "device BVH build needs at least 2 primitives";
-    return RP_EINVAL;
-  }
-  if (node_format != rpl::NODES_F32 && node_format != rpl::NODES_Q8) {
-    err = "unknown node format";
-    return RP_EINVAL;
-  }
-  if (node_format == rpl::NODES_Q8 && !(in.amax <= rpl::COORD_MAX)) {
-    err = "primitive coordinates beyond +-2^54 (or infinite) are not supported by the quantized nodes";
-    return RP_EINVAL;
-  }
-  if (max_leaf < 1 || max_leaf > rpl::LEAF_MAX) {
-    err = "max_leaf out of range";
-    return RP_EINVAL;
-  }
-  std::vector<void*> tmp;
-  hipError_t e = hipSuccess;
-  auto alloc = [&](void** p, size_t bytes) {
-    if (e != hipSuccess) return;
-    e = hipMalloc(p, bytes);
-    if (e == hipSuccess) tmp.push_back(*p);
-    else *p = nullptr;
-  };
-  Box6* d_boxes = nullptr;
-  rpl::Prim* d_prims_in = nullptr;
-  rpl::PrimRef* d_refs_in = nullptr;
-  uint64_t *d_keys = nullptr, *d_keys_sorted = nullptr;
-  uint32_t *d_order = nullptr, *d_left = nullptr, *d_right = nullptr, *d_pin = nullptr, *d_pleaf = nullptr;
-  uint32_t *d_first = nullptr, *d_last = nullptr, *d_visits = nullptr, *d_ctr = nullptr;
-  Box6* d_nboxes = nullptr;
-  Frontier *d_fa = nullptr, *d_fb = nullptr;
-  alloc((void**)&d_boxes, sizeof(Box6) * n);
-  alloc((void**)&d_prims_in, sizeof(rpl::Prim) * n);
-  alloc((void**)&d_refs_in, sizeof(rpl::PrimRef) * n);
-  alloc((void**)&d_keys, sizeof(uint64_t) * n);
-  alloc((void**)&d_keys_sorted, sizeof(uint64_t) * n);
-  alloc((void**)&d_order, sizeof(uint32_t) * n);
-  alloc((void**)&d_left, sizeof(uint32_t) * n);
-  alloc((void**)&d_right, sizeof(uint32_t) * n);
-  alloc((void**)&d_pin, sizeof(uint32_t) * n);
-  alloc((void**)&d_pleaf, sizeof(uint32_t) * n);
-  alloc((void**)&d_first, sizeof(uint32_t) * n);
-  alloc((void**)&d_last, sizeof(uint32_t) * n);
-  alloc((void**)&d_visits, sizeof(uint32_t) * n);
-  alloc((void**)&d_ctr, sizeof(uint32_t) * 4);
-  alloc((void**)&d_nboxes, sizeof(Box6) * n);
-  alloc((void**)&d_fa, sizeof(Frontier) * n);
-  alloc((void**)&d_fb, sizeof(Frontier) * n);
-  // outputs: at most n - 1 wide nodes (each inner wide node has >= 2 children)
-  const size_t node_bytes = node_format == rpl::NODES_Q8 ? sizeof(rpl::Node4Q) : sizeof(rpl::Node4);
-  if (e == hipSuccess) e = hipMalloc(&out.d_nodes, node_bytes * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&out.d_prims, sizeof(rpl::Prim) * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&out.d_prim_refs, sizeof(rpl::PrimRef) * n);
-  void* d_sort_tmp = nullptr;
-  size_t sort_bytes = 0;
-  auto cleanup = [&](int code, const std::string& msg) {
-    for (void* p : tmp) (void)hipFree(p);
-    if (d_sort_tmp) (void)hipFree(d_sort_tmp);
-    if (code != RP_OK) {
-      if (out.d_nodes) (void)hipFree(out.d_nodes);
-      if (out.d_prims) (void)hipFree(out.d_prims);
-      if (out.d_prim_refs) (void)hipFree(out.d_prim_refs);
-      out = GpuTree{};
-      err = msg;
+  if (n < 2) return failed(err, RP_EINVAL, "device BVH build needs at least 2 primitives");
+  if (node_format != rpl::NODES_F32 && node_format != rpl::NODES_Q8) return failed(err, RP_EINVAL, "unknown node format");
+  if (node_format == rpl::NODES_Q8 && !(in.amax <= rpl::COORD_MAX))
+    return failed(err, RP_EINVAL, "primitive coordinates beyond +-2^54 (or infinite) are not supported by the quantized nodes");
+  if (max_leaf < 1 || max_leaf > rpl::LEAF_MAX) return failed(err, RP_EINVAL, "max_leaf out of range");
+  // the prologue: the upload, the Morton keys and their sort (the unsorted keys and the sort's scratch end with it)
+  const bool ploc = algo == GPU_PLOC;
+  Sorted s;
+  Outputs o;
+  s.n = n;
+  {
+    DevBuf<uint64_t> keys;
+    DevBuf<uint32_t> idx;  // PLOC sorts (key, primitive) pairs
+    DevBuf<uint8_t> sort_tmp;
+    hipError_t e = hipSuccess;
+    alloc(e, s.boxes, n);
+    alloc(e, s.prims, n);
+    alloc(e, s.refs, n);
+    alloc(e, keys, n);
+    alloc(e, s.keys, n);
+    alloc(e, s.order, n);
+    if (ploc) alloc(e, idx, n);
+    alloc(e, o.nodes, (node_format == rpl::NODES_Q8 ? sizeof(rpl::Node4Q) : sizeof(rpl::Node4)) * n);
+    alloc(e, o.prims, n);
+    alloc(e, o.refs, n);
+    if (e != hipSuccess) return alloc_failed(RadixSrc::build, e, err);
+    e = hipMemcpy(s.boxes.get(), in.boxes.data(), sizeof(Box6) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s.prims.get(), in.prims.data(), sizeof(rpl::Prim) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s.refs.get(), in.refs.data(), sizeof(rpl::PrimRef) * n, hipMemcpyHostToDevice);
+    RPG_CHECK("upload (device BVH build)");
+    const double3 cmin = make_double3(in.cmin[0], in.cmin[1], in.cmin[2]);
+    double sc[3];
+    for (int k = 0; k < 3; k++) {
+      const double ext = in.cmax[k] - in.cmin[k];
+      sc[k] = ext > 0.0 ? 1024.0 / ext : 0.0;
     }
-    return code;
-  };
-  if (e != hipSuccess) return cleanup(RP_ENOMEM, std::string("hipMalloc (device BVH build): ") + hipGetErrorString(e));
-#define RPG_CHECK(what)                                                                              \
-  do {                                                                                               \
-    e = hipGetLastError();                                                                           \
-    if (e != hipSuccess) return cleanup(RP_EHIP, std::string(what) + ": " + hipGetErrorString(e));   \
-  } while (0)
-  e = hipMemcpy(d_boxes, in.boxes.data(), sizeof(Box6) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_prims_in, in.prims.data(), sizeof(rpl::Prim) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_refs_in, in.refs.data(), sizeof(rpl::PrimRef) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_visits, 0, sizeof(uint32_t) * n);
-  if (e == hipSuccess) e = hipMemset(d_ctr, 0, sizeof(uint32_t) * 4);
-  if (e != hipSuccess) return cleanup(RP_EHIP, std::string("upload (device BVH build): ") + hipGetErrorString(e));
-
-  const unsigned B = 256;
-  double3 cmin = make_double3(in.cmin[0], in.cmin[1], in.cmin[2]);
-  double sc[3];
-  for (int k = 0; k < 3; k++) {
-    const double ext = in.cmax[k] - in.cmin[k];
-    sc[k] = ext > 0.0 ? 1024.0 / ext : 0.0;
-  }
-  if (algo == GPU_PLOC) {
-    hipLaunchKernelGGL(morton63_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_boxes, cmin,
-                       make_double3(sc[0], sc[1], sc[2]), d_keys, d_left);
-    RPG_CHECK("morton");
-    e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys, d_keys_sorted, d_left, d_order, (int)n, 0, 63);
-    if (e == hipSuccess) e = hipMalloc(&d_sort_tmp, sort_bytes);
-    if (e == hipSuccess)
-      e = hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, sort_bytes, d_keys, d_keys_sorted, d_left, d_order, (int)n, 0, 63);
-    if (e != hipSuccess) return cleanup(RP_EHIP, std::string("radix sort: ") + hipGetErrorString(e));
-    out.node_format = node_format;
-    out.qbound = rpl::qbound(in.amax);
-    std::string perr;
-    const int rc = build_ploc(n, d_order, d_boxes, d_prims_in, d_refs_in, max_leaf, cost_traverse, node_format,
-                                std::max(1u, align), out, perr);
-    return cleanup(rc, perr);
-  }
-  hipLaunchKernelGGL(morton_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_boxes, cmin,
-                     make_double3(sc[0], sc[1], sc[2]), d_keys);
-  RPG_CHECK("morton");
-  e = hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, d_keys, d_keys_sorted, (int)n, 0, 62);
-  if (e == hipSuccess) e = hipMalloc(&d_sort_tmp, sort_bytes);
-  if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortKeys(d_sort_tmp, sort_bytes, d_keys, d_keys_sorted, (int)n, 0, 62);
-  if (e != hipSuccess) return cleanup(RP_EHIP, std::string("radix sort: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(order_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_keys_sorted, d_order);
-  RPG_CHECK("order");
-  hipLaunchKernelGGL(radix_tree_kernel, dim3(grid(n - 1, B)), dim3(B), 0, nullptr, n, d_keys_sorted, d_left, d_right,
-                     d_pin, d_pleaf, d_first, d_last);
-  RPG_CHECK("radix tree");
-  hipLaunchKernelGGL(boxes_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_boxes, d_order, d_left, d_right,
-                     d_pin, d_pleaf, d_nboxes, d_visits);
-  RPG_CHECK("boxes");
-  // collapse, level by level from the root (binary inner node 0 -> wide node 0)
-  const Frontier root{0u, 0u};
-  const uint32_t one = 1u;
-  e = hipMemcpy(d_fa, &root, sizeof root, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_ctr, &one, sizeof one, hipMemcpyHostToDevice);  // wide node 0 taken
-  if (e != hipSuccess) return cleanup(RP_EHIP, std::string("collapse setup: ") + hipGetErrorString(e));
-  uint32_t n_cur = 1, depth = 0;
-  for (;;) {
-    e = hipMemset(d_ctr + 1, 0, sizeof(uint32_t));
-    if (e != hipSuccess) return cleanup(RP_EHIP, std::string("collapse: ") + hipGetErrorString(e));
-    if (node_format == rpl::NODES_Q8)
-      hipLaunchKernelGGL(collapse_kernel<rpl::NODES_Q8>, dim3(grid(n_cur, B)), dim3(B), 0, nullptr, d_fa, n_cur, d_fb,
-                         d_ctr, max_leaf, d_boxes, d_order, d_left, d_right, d_first, d_last, d_nboxes, out.d_nodes);
+    const double3 scale = make_double3(sc[0], sc[1], sc[2]);
+    if (ploc)
+      launch(morton63_kernel, n, n, s.boxes.get(), cmin, scale, keys.get(), idx.get());
     else
-      hipLaunchKernelGGL(collapse_kernel<rpl::NODES_F32>, dim3(grid(n_cur, B)), dim3(B), 0, nullptr, d_fa, n_cur, d_fb,
-                         d_ctr, max_leaf, d_boxes, d_order, d_left, d_right, d_first, d_last, d_nboxes, out.d_nodes);
-    RPG_CHECK("collapse");
-    uint32_t ctr[4];
-    e = hipMemcpy(ctr, d_ctr, sizeof ctr, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return cleanup(RP_EHIP, std::string("collapse: ") + hipGetErrorString(e));
-    if (ctr[0] > n) return cleanup(RP_EINTERNAL, "device BVH build: wide node overflow");
-    if (ctr[1] == 0) {
-      out.n_nodes = ctr[0];
-      out.n_leaves = ctr[2];
-      break;
+      launch(morton_kernel, n, n, s.boxes.get(), cmin, scale, keys.get());
+    RPG_CHECK("morton");
+    size_t sort_bytes = 0;
+    auto sort = [&](void* tmp) {  // tmp == nullptr: the scratch size only
+      return ploc ? hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, keys.get(), s.keys.get(), idx.get(), s.order.get(),
+                                                       (int)n, 0, 63)
+                  : hipcub::DeviceRadixSort::SortKeys(tmp, sort_bytes, keys.get(), s.keys.get(), (int)n, 0, 62);
+    };
+    e = sort(nullptr);
+    if (e == hipSuccess) sort_tmp.alloc(sort_bytes, &e);
+    if (e == hipSuccess) e = sort(sort_tmp.get());
+    RPG_CHECK("radix sort");
+    if (!ploc) {
+      launch(order_kernel, n, n, s.keys.get(), s.order.get());
+      RPG_CHECK("order");
     }
-    depth++;
-    n_cur = ctr[1];
-    std::swap(d_fa, d_fb);
   }
-  out.max_depth = depth;
+  const int rc = ploc ? build_ploc(s, max_leaf, cost_traverse, node_format, std::max(1u, align), o, out, err)
+                      : build_lbvh(s, max_leaf, node_format, o, out, err);
+  if (rc != RP_OK) {
+    out = GpuTree{};
+    return rc;
+  }
   out.node_format = node_format;
   out.qbound = rpl::qbound(in.amax);
-  hipLaunchKernelGGL(permute_kernel, dim3(grid(n, B)), dim3(B), 0, nullptr, n, d_order, d_prims_in, d_refs_in,
-                     out.d_prims, out.d_prim_refs);
-  RPG_CHECK("permute");
-  e = hipDeviceSynchronize();
-  if (e != hipSuccess) return cleanup(RP_EHIP, std::string("device BVH build: ") + hipGetErrorString(e));
-#undef RPG_CHECK
-  return cleanup(RP_OK, "");
+  out.d_nodes = o.nodes.release();
+  out.d_prims = o.prims.release();
+  out.d_prim_refs = o.refs.release();
+  return RP_OK;
 }
 
 }  // namespace rpg

@@ -1,4 +1,5 @@
-// rp_hip_util.h -- what the C-ABI's translation units (rp_scene.cpp, rp_render.cpp, rp_gather.cpp) share: the error
+// rp_hip_util.h -- what the C-ABI's translation units (rp_scene.cpp, rp_render.cpp, rp_gather.cpp) share, and of which
+// the device tree builder (rp_bvh_gpu.hip) uses the owner of device memory: the error
 // slot, the HIP / RCCL call checks, and the owners of device memory, streams, events and communicators.  Internal to
 // librp.so: nothing here is exported.
 #pragma once
@@ -92,6 +93,11 @@ class DevBuf {
     reset();
     p_ = p;
     cap_ = n;
+  }
+  // hand the pointer out: the caller frees it (the device tree builder's outputs leave it this way)
+  T* release() {
+    cap_ = 0;
+    return std::exchange(p_, nullptr);
   }
   T* get() const { return p_; }
   uint64_t capacity() const { return cap_; }
