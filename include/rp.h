@@ -497,6 +497,68 @@ int rp_denoise_device(const rp_denoise_params* params, uint32_t width, uint32_t 
 int rp_denoise(const rp_denoise_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
                const double* normal, const double* albedo, const double* depth, double* out, double* seconds);
 
+/* Per-pixel variance from the batch sums: the variance of every pixel's mean, estimated from the spread of its sample
+ * batches.  It costs no ray: a frame of more than one batch per pixel (spp > samples_per_stream) leaves every batch's
+ * sample sum in its workspace, and this pass reads them there.  For error maps, stopping rules and rp_denoise_var.
+ * DESIGN.md 4.12 has the derivation.
+ *   Definition.  N = samples_per_stream (0: RP_SAMPLES_PER_STREAM), B = ceil(spp / N) batches, batch b holds
+ *   n_b = min(N, spp - b*N) samples and S_b is the sum of its samples' radiance.  Per channel, in IEEE binary64, in the
+ *   order written and without contraction:
+ *     x   = (((0.0 + S_0) + S_1) + ...) / spp            -- rp_render's pixel, bit for bit
+ *     e_b = S_b / spp - x * ((double)n_b / spp)
+ *     acc = the sum of e_b * e_b from 0.0 in b order
+ *     var = acc * ((double)B / (double)(B - 1))
+ *   With equal batches e_b = (m_b - x) / B for the batch means m_b = S_b / N, and var = sum (m_b - x)^2 / (B (B - 1)):
+ *   the unbiased estimate of the variance of the mean of B independent batch means.
+ * rp_render_variance_device_ws reads the sums that the LAST render of `params` on `workspace` (NULL = the scene's) left
+ * there -- rp_render_device[_ws] with one frame per launch; the caller orders the pass after that render on streams, and
+ * before the workspace's next render.  d_shard_var: 3 doubles per slot in the render's compact shard order
+ * (rp_shard_pixel_count slots); slots of edge tiles outside the frame are not written.  Asynchronous on `stream`, never
+ * allocates or synchronises (capturable); an empty shard launches nothing.  params.shard, num_shards, tile_w, tile_h and
+ * shard_map are honoured: a balanced shard uses the plan the beauty render left in the workspace, as rp_render_aov does.
+ * RP_EINVAL: B < 2 (nothing to take a spread of), a workspace whose batch reservation (rp_workspace_reserve) does not
+ * cover the shard's slots x B, a balanced shard without a plan, NULL d_shard_var.  The sums of a multi-frame launch
+ * (rp_render_frames_device_ws) are not supported.
+ * The shard buffer is laid out like the render's rgb: gathered shards assemble with rp_frame_assemble[_ws] at
+ * words_per_slot = 6, and rp_shard_unpack[_map] unpacks it with channels = 3. */
+int rp_render_variance_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_render_params* params,
+                                 double* d_shard_var, void* stream);
+
+/* Variance-guided denoiser: rp_denoise with the colour stop scaled by each pixel's measured noise instead of one
+ * sigma_color.  Where a reflection or a sky seen through glass is deterministic the variance is about zero, the stop is
+ * tight and the detail stays; where a pixel is noisy it blurs.  var is a full frame in frame order,
+ * 3 doubles per pixel: the variance of rgb's pixel per channel, as rp_render_variance_device_ws defines it.
+ *   Parameters: base is rp_denoise's, with base.sigma_color ignored; a zero field takes its default, params = NULL
+ *   means all defaults.
+ *     sigma_var  3.0   sigma_v  (> 0, finite)
+ *     var_eps    1e-6  eps_v    (> 0, finite)
+ *   Definition.  Everything in rp_denoise's definition stands, except:
+ *     Every pixel also carries v, the variance of its c summed over the channels.  Initially
+ *       v = (x + y) + z of var / ((albedo + eps) * (albedo + eps)) per channel; albedo NULL: of var itself.
+ *     Level l (step s), pixel p, first a prefilter of v: the taps dy = -1..1 (outer), dx = -1..1 (inner) at
+ *       q = p + s*(dx, dy); a tap counts if it lies inside the frame and nn_q > 0 (normal NULL: every tap inside the
+ *       frame); its weight is kg[|dx|] * kg[|dy|], kg = {1/2, 1/4}; g += weight * v_q and gw += weight from 0.0 in tap
+ *       order; vf = g / gw.
+ *     w_c = rat(|c_p - c_q|^2 / ((sigma_v*sigma_v) * (vf + eps_v))), at every level and never disabled.
+ *     Beside sw and acc, every tap adds (w*w) * v_q to vacc (from 0.0); v' = vacc / (sw*sw).
+ *     A pixel with nn == 0 keeps its c and its v.
+ *   The prefilter lies on the level's own sub-lattice (step s, not 1): its taps are among the 5 x 5 taps.
+ * rp_denoise_var_device, rp_denoise_var: as rp_denoise_device and rp_denoise, with d_var / var beside rgb (NULL:
+ * RP_EINVAL; out and scratch must not alias it).  d_scratch: rp_denoise_var_scratch_bytes bytes, 8-byte aligned: two
+ * colour and two variance buffers, 2 x (24 + 8) bytes per pixel. */
+typedef struct rp_denoise_var_params {
+  rp_denoise_params base;
+  double sigma_var, var_eps;
+} rp_denoise_var_params;
+int rp_denoise_var_params_init(rp_denoise_var_params* params);
+int rp_denoise_var_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+int rp_denoise_var_device(const rp_denoise_var_params* params, uint32_t width, uint32_t height, const double* d_rgb,
+                          const double* d_var, const double* d_normal, const double* d_albedo, const double* d_depth,
+                          double* d_out, void* d_scratch, void* stream);
+int rp_denoise_var(const rp_denoise_var_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
+                   const double* var, const double* normal, const double* albedo, const double* depth, double* out,
+                   double* seconds);
+
 /* Output stage on the device: the reference's to_srgb_u8 (utility.rs:212-220, alpha 255) of every slot of
  * a compact shard buffer, bytes in tga::save's pixel order B, G, R, A (image.rs:116-137), so a gathered
  * and de-interleaved frame is the body of the reference's output.tga (18-byte header: rph_tga_save).

@@ -163,6 +163,16 @@ int rph_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bo
  * NULL rgb or out, a zero size, a side above 65535, out aliasing an input and parameters out of range. */
 int rph_denoise(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* rgb, const double* normal,
                 const double* albedo, const double* depth, double* out);
+/* The variance-guided denoiser on the CPU (include/rp.h rp_denoise_var: the definition), the same loop over the same
+ * header with the variance carried along.  var: a full frame, 3 doubles per pixel, required; the rest as rph_denoise. */
+int rph_denoise_var(const rp_denoise_var_params* params, uint32_t width, uint32_t height, const double* rgb,
+                    const double* var, const double* normal, const double* albedo, const double* depth, double* out);
+
+/* The per-pixel variance pass on the CPU (include/rp.h rp_render_variance_device_ws: the definition): a plain loop over
+ * raytracing-potato_amd/csrc/rp_variance.h, the header the device kernel compiles.  sums: n_pixels x B x 3 doubles,
+ * pixel i's batch b at (i*B + b)*3 with B = ceil(spp / samples_per_stream) (0: RP_SAMPLES_PER_STREAM); var: n_pixels x 3.
+ * RP_EINVAL for B < 2 and NULL buffers. */
+int rph_batch_variance(uint32_t spp, uint32_t samples_per_stream, uint64_t n_pixels, const double* sums, double* var);
 
 const char* rph_last_error(void);
 

@@ -11,6 +11,11 @@
 // p + s (dx, dy) and returns false where that lies outside the frame: the kernel reads a dense LDS tile of the pixel's
 // residue class mod s, the host loop reads the frame.  Records come by value and by reference to locals only (scalar
 // registers on the device after inlining: 0 B of scratch per lane).
+//
+// The variance-guided filter (include/rp.h rp_denoise_var*) is the same step with VAR = true: a pixel
+// also carries the variance v of its colour, the colour stop's scale comes from a 3 x 3 prefilter of v on the level's
+// own taps instead of sigma_color, and v is filtered along with the colour.  VAR = false is the guided denoiser, its
+// expressions untouched.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -56,6 +61,26 @@ inline bool resolve(const rp_denoise_params* in, rp_denoise_params& p) {
   return p.sigma_color - p.sigma_color == 0.0;
 }
 
+// the variance-guided filter's: base.sigma_color is ignored, sigma_var and var_eps are positive and finite
+static constexpr double DEF_SIGMA_VAR = 3.0, DEF_VAR_EPS = 1e-6;
+inline void defaults(rp_denoise_var_params& p) {
+  defaults(p.base);
+  p.sigma_var = DEF_SIGMA_VAR;
+  p.var_eps = DEF_VAR_EPS;
+}
+inline bool resolve(const rp_denoise_var_params* in, rp_denoise_var_params& p) {
+  rp_denoise_params base{};
+  if (in) base = in->base;
+  base.sigma_color = 0.0;
+  if (!resolve(&base, p.base)) return false;
+  p.sigma_var = in && in->sigma_var != 0.0 ? in->sigma_var : DEF_SIGMA_VAR;
+  p.var_eps = in && in->var_eps != 0.0 ? in->var_eps : DEF_VAR_EPS;
+  const double pos[2] = {p.sigma_var, p.var_eps};
+  for (double x : pos)
+    if (!(x > 0.0) || x - x != 0.0) return false;
+  return true;
+}
+
 // ---- one level's constants (made on the host for both sides)
 enum : uint32_t { HAS_NORMAL = 1, HAS_ALBEDO = 2, HAS_DEPTH = 4, HAS_COLOR = 8 };
 struct Level {
@@ -64,8 +89,9 @@ struct Level {
   int32_t step;      // s = 2^l
   double sz;         // sigma_z
   double sa2;        // sigma_a sigma_a
-  double sc2;        // sigma_c,l sigma_c,l with sigma_c,l = sigma_c / 2^l
+  double sc2;        // sigma_c,l sigma_c,l with sigma_c,l = sigma_c / 2^l; variance-guided: sigma_v sigma_v
   double eps;
+  double veps;       // variance-guided: var_eps
 };
 inline Level make_level(const rp_denoise_params& p, uint32_t l, bool normal, bool albedo, bool depth) {
   Level L;
@@ -78,6 +104,15 @@ inline Level make_level(const rp_denoise_params& p, uint32_t l, bool normal, boo
   const double scl = p.sigma_color / (double)(1u << l);
   L.sc2 = scl * scl;
   L.eps = p.albedo_eps;
+  L.veps = 0.0;
+  return L;
+}
+// the variance-guided filter's level: the colour term is always on and its scale is the same at every level
+inline Level make_level(const rp_denoise_var_params& p, uint32_t l, bool normal, bool albedo, bool depth) {
+  Level L = make_level(p.base, l, normal, albedo, depth);
+  L.flags |= HAS_COLOR;
+  L.sc2 = p.sigma_var * p.sigma_var;
+  L.veps = p.var_eps;
   return L;
 }
 
@@ -87,6 +122,7 @@ struct Px {
   double nx, ny, nz, nn;
   double ax, ay, az;
   double z;
+  double v;  // variance-guided: the variance of c, summed over the channels
 };
 
 RPDN_FN double len2(double x, double y, double z) { return (x * x + y * y) + z * z; }
@@ -97,16 +133,21 @@ RPDN_FN double rat(double x2) {
 // demodulation and its inverse, per channel
 RPDN_FN double demod(double rgb, double albedo, double eps) { return rgb / (albedo + eps); }
 RPDN_FN double remod(double c, double albedo, double eps) { return c * (albedo + eps); }
+// variance-guided: a channel's variance under demodulation, and a pixel's initial v from its three
+RPDN_FN double demod_var(double var, double albedo, double eps) { return var / ((albedo + eps) * (albedo + eps)); }
+RPDN_FN double sum3(double x, double y, double z) { return (x + y) + z; }
 // the kernel k = {3/8, 1/4, 1/16} at |d|
 RPDN_FN double kern(int d) {
   const int a = d < 0 ? -d : d;
   return a == 0 ? 0.375 : (a == 1 ? 0.25 : 0.0625);
 }
+// variance-guided: the prefilter's kernel kg = {1/2, 1/4} at |d| <= 1
+RPDN_FN double kern_g(int d) { return d == 0 ? 0.5 : 0.25; }
 // a pixel the filter leaves alone (background, misses): its normal is zero
 RPDN_FN bool passes(const Level& L, const Px& p) { return (L.flags & HAS_NORMAL) && p.nn == 0.0; }
 
-// w = (((h w_n) w_z) w_a) w_c of the tap q of pixel p
-RPDN_FN double tap_weight(const Level& L, const Px& p, const Px& q, double h, bool centre) {
+// w = (((h w_n) w_z) w_a) w_c of the tap q of pixel p; sc2 divides the squared colour distance
+RPDN_FN double tap_weight(const Level& L, const Px& p, const Px& q, double h, bool centre, double sc2) {
   double wn = 1.0, wz = 1.0, wa = 1.0, wc = 1.0;
   if ((L.flags & HAS_NORMAL) && !centre) {
     const double d = (p.nx * q.nx + p.ny * q.ny) + p.nz * q.nz;
@@ -123,20 +164,42 @@ RPDN_FN double tap_weight(const Level& L, const Px& p, const Px& q, double h, bo
     wz = rat(x * x);
   }
   if (L.flags & HAS_ALBEDO) wa = rat(len2(p.ax - q.ax, p.ay - q.ay, p.az - q.az) / L.sa2);
-  if (L.flags & HAS_COLOR) wc = rat(len2(p.cx - q.cx, p.cy - q.cy, p.cz - q.cz) / L.sc2);
+  if (L.flags & HAS_COLOR) wc = rat(len2(p.cx - q.cx, p.cy - q.cy, p.cz - q.cz) / sc2);
   return (((h * wn) * wz) * wa) * wc;
 }
 
-// c' of pixel p: the 5 x 5 taps at step s, dy outer and dx inner, sums from 0.0 in tap order
-template <class Tap>
-RPDN_FN void level_step(const Level& L, const Px& p, Tap tap, double& ox, double& oy, double& oz) {
+// c' (and, VAR, v') of pixel p: the 5 x 5 taps at step s, dy outer and dx inner, sums from 0.0 in tap order.
+// VAR: first vf = g / gw over the 3 x 3 taps at the same step that lie in the frame and are no pass-through pixels,
+// weights kg kg; the colour distance is divided by (sigma_v sigma_v) (vf + var_eps); vacc sums (w w) v_q and
+// v' = vacc / (sw sw).
+template <bool VAR, class Tap>
+RPDN_FN void level_step_v(const Level& L, const Px& p, Tap tap, double& ox, double& oy, double& oz, double& ov) {
   if (passes(L, p)) {
     ox = p.cx;
     oy = p.cy;
     oz = p.cz;
+    if (VAR) ov = p.v;
     return;
   }
-  double sw = 0.0, ax = 0.0, ay = 0.0, az = 0.0;
+  double sc2 = L.sc2;
+  if (VAR) {
+    double g = 0.0, gw = 0.0;
+    for (int dy = -1; dy <= 1; dy++) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+      for (int dx = -1; dx <= 1; dx++) {
+        Px q;
+        if (!tap(dx, dy, q)) continue;
+        if ((L.flags & HAS_NORMAL) && !(q.nn > 0.0)) continue;
+        const double k = kern_g(dx) * kern_g(dy);
+        g = g + k * q.v;
+        gw = gw + k;
+      }
+    }
+    sc2 = L.sc2 * (g / gw + L.veps);
+  }
+  double sw = 0.0, ax = 0.0, ay = 0.0, az = 0.0, av = 0.0;
   for (int dy = -2; dy <= 2; dy++) {
 #if defined(__HIPCC__)
 #pragma unroll
@@ -145,16 +208,23 @@ RPDN_FN void level_step(const Level& L, const Px& p, Tap tap, double& ox, double
       Px q;
       if (!tap(dx, dy, q)) continue;
       const double h = kern(dx) * kern(dy);
-      const double w = tap_weight(L, p, q, h, dx == 0 && dy == 0);
+      const double w = tap_weight(L, p, q, h, dx == 0 && dy == 0, sc2);
       sw = sw + w;
       ax = ax + w * q.cx;
       ay = ay + w * q.cy;
       az = az + w * q.cz;
+      if (VAR) av = av + (w * w) * q.v;
     }
   }
   ox = ax / sw;
   oy = ay / sw;
   oz = az / sw;
+  if (VAR) ov = av / (sw * sw);
+}
+template <class Tap>
+RPDN_FN void level_step(const Level& L, const Px& p, Tap tap, double& ox, double& oy, double& oz) {
+  double ov;
+  level_step_v<false>(L, p, tap, ox, oy, oz, ov);
 }
 
 }  // namespace rpdn

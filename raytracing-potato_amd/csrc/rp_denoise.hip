@@ -15,6 +15,10 @@
 // it loads (rgb / (albedo + eps), once per loaded pixel), the last one remodulates as it stores and copies the
 // pass-through pixels' rgb; levels in between ping-pong between two colour buffers in the caller's scratch.  nn is made
 // once per loaded pixel.  No allocation, no synchronisation, nothing but launches on the caller's stream.
+//
+// The variance-guided filter (rp_denoise_var*) is the instantiation VAR = true of the same kernel: the
+// pixel record grows from 11 to 12 doubles by the variance v (made from var and the albedo as the first level loads,
+// ping-ponged in scratch beside the colour after it), and the 3 x 3 prefilter of v reads taps the tile already holds.
 #include "rp_hip_util.h"  // first: the HIP runtime defines the qualifiers rp_denoise.h uses
 
 #include "rp_denoise.h"
@@ -25,7 +29,7 @@ namespace rpdn {
 
 constexpr int TX = 32, TY = 8, HALO = 2, LW = TX + 2 * HALO, LH = TY + 2 * HALO, LN = LW * LH;
 constexpr int DN_BLOCK = TX * TY;
-enum { F_CX, F_CY, F_CZ, F_NX, F_NY, F_NZ, F_NN, F_AX, F_AY, F_AZ, F_Z, F_N };
+enum { F_CX, F_CY, F_CZ, F_NX, F_NY, F_NZ, F_NN, F_AX, F_AY, F_AZ, F_Z, F_N, F_V = F_N, F_NV };  // VAR: one more
 
 struct DnArgs {
   Level L;
@@ -38,19 +42,27 @@ struct DnArgs {
   const double* albedo;
   const double* depth;
   double* out;
+  // VAR: the frame's variance (3 per pixel; the first level's input), the later levels' input v and this level's v'
+  // (1 per pixel, scratch; the last level writes none)
+  const double* var;
+  const double* vin;
+  double* vout;
 };
 
+template <bool VAR>
 __device__ __forceinline__ Px lds_px(const double (*t)[LN], int e, uint32_t flags) {
   Px q = {};
   q.cx = t[F_CX][e], q.cy = t[F_CY][e], q.cz = t[F_CZ][e];
   if (flags & HAS_NORMAL) q.nx = t[F_NX][e], q.ny = t[F_NY][e], q.nz = t[F_NZ][e], q.nn = t[F_NN][e];
   if (flags & HAS_ALBEDO) q.ax = t[F_AX][e], q.ay = t[F_AY][e], q.az = t[F_AZ][e];
   if (flags & HAS_DEPTH) q.z = t[F_Z][e];
+  if (VAR) q.v = t[F_V][e];
   return q;
 }
 
+template <bool VAR>
 __global__ void __launch_bounds__(DN_BLOCK) denoise_level(const DnArgs A) {
-  __shared__ double tile[F_N][LN];
+  __shared__ double tile[VAR ? F_NV : F_N][LN];
   const Level L = A.L;
   const uint32_t s = (uint32_t)L.step, flags = L.flags;
   // block -> residue class (ri, rj) and tile (tx, ty) of its sub-lattice; the class's pixels are (ri + s u, rj + s v)
@@ -64,11 +76,15 @@ __global__ void __launch_bounds__(DN_BLOCK) denoise_level(const DnArgs A) {
     if (u < 0 || u >= sw || v < 0 || v >= sh) continue;  // outside the frame: a tap the lanes skip, never read
     const uint64_t px = (uint64_t)(rj + s * (uint32_t)v) * A.W + (ri + s * (uint32_t)u);
     double cx = A.in[3 * px], cy = A.in[3 * px + 1], cz = A.in[3 * px + 2];
+    double vx = 0.0, vy = 0.0, vz = 0.0;
+    if (VAR && A.first) vx = A.var[3 * px], vy = A.var[3 * px + 1], vz = A.var[3 * px + 2];
     if (flags & HAS_ALBEDO) {
       const double ax = A.albedo[3 * px], ay = A.albedo[3 * px + 1], az = A.albedo[3 * px + 2];
       tile[F_AX][e] = ax, tile[F_AY][e] = ay, tile[F_AZ][e] = az;
       if (A.first) cx = demod(cx, ax, L.eps), cy = demod(cy, ay, L.eps), cz = demod(cz, az, L.eps);
+      if (VAR && A.first) vx = demod_var(vx, ax, L.eps), vy = demod_var(vy, ay, L.eps), vz = demod_var(vz, az, L.eps);
     }
+    if (VAR) tile[F_V][e] = A.first ? sum3(vx, vy, vz) : A.vin[px];
     tile[F_CX][e] = cx, tile[F_CY][e] = cy, tile[F_CZ][e] = cz;
     if (flags & HAS_NORMAL) {
       const double nx = A.normal[3 * px], ny = A.normal[3 * px + 1], nz = A.normal[3 * px + 2];
@@ -82,17 +98,17 @@ __global__ void __launch_bounds__(DN_BLOCK) denoise_level(const DnArgs A) {
   const int u = u0 + lx, v = v0 + ly;
   if (u >= sw || v >= sh) return;
   const int e0 = (ly + HALO) * LW + lx + HALO;
-  const Px p = lds_px(tile, e0, flags);
-  double ox, oy, oz;
-  level_step(
+  const Px p = lds_px<VAR>(tile, e0, flags);
+  double ox, oy, oz, ov;
+  level_step_v<VAR>(
       L, p,
       [&](int dx, int dy, Px& q) {
         const int uu = u + dx, vv = v + dy;
         if (uu < 0 || uu >= sw || vv < 0 || vv >= sh) return false;
-        q = lds_px(tile, e0 + dy * LW + dx, flags);
+        q = lds_px<VAR>(tile, e0 + dy * LW + dx, flags);
         return true;
       },
-      ox, oy, oz);
+      ox, oy, oz, ov);
   const uint64_t px = (uint64_t)(rj + s * (uint32_t)v) * A.W + (ri + s * (uint32_t)u);
   if (A.last) {
     if (passes(L, p)) {  // rgb itself, bit for bit
@@ -102,6 +118,7 @@ __global__ void __launch_bounds__(DN_BLOCK) denoise_level(const DnArgs A) {
     }
   }
   A.out[3 * px] = ox, A.out[3 * px + 1] = oy, A.out[3 * px + 2] = oz;
+  if (VAR && !A.last) A.vout[px] = ov;
 }
 
 }  // namespace rpdn
@@ -121,6 +138,102 @@ int check_frame(uint32_t width, uint32_t height) {
   if (width > DIM_MAX || height > DIM_MAX) return fail(RP_EINVAL, "width and height must be <= 65535");
   return RP_OK;
 }
+
+// What rp_denoise_device and rp_denoise_var_device refuse about their buffers (d_var NULL: the former).
+int check_buffers(uint32_t width, uint32_t height, const double* d_rgb, const double* d_var, const double* d_normal,
+                  const double* d_albedo, const double* d_depth, const double* d_out, const void* d_scratch,
+                  uint64_t scratch_bytes) {
+  const uint64_t n = (uint64_t)width * height, b3 = 3 * n * sizeof(double), b1 = n * sizeof(double);
+  if (overlaps(d_out, b3, d_rgb, b3) || overlaps(d_out, b3, d_normal, b3) || overlaps(d_out, b3, d_albedo, b3) ||
+      overlaps(d_out, b3, d_depth, b1) || overlaps(d_out, b3, d_var, b3))
+    return fail(RP_EINVAL, "out must not alias an input");
+  if (overlaps(d_scratch, scratch_bytes, d_out, b3) || overlaps(d_scratch, scratch_bytes, d_rgb, b3) ||
+      overlaps(d_scratch, scratch_bytes, d_normal, b3) || overlaps(d_scratch, scratch_bytes, d_albedo, b3) ||
+      overlaps(d_scratch, scratch_bytes, d_depth, b1) || overlaps(d_scratch, scratch_bytes, d_var, b3))
+    return fail(RP_EINVAL, "scratch must not alias an input or out");
+  if (reinterpret_cast<uintptr_t>(d_scratch) % sizeof(double)) return fail(RP_EINVAL, "scratch must be 8-byte aligned");
+  return RP_OK;
+}
+
+// One launch per level of P (resolved: rp_denoise_params, or rp_denoise_var_params with VAR), ping-ponging between the
+// two colour buffers -- and, VAR, the two variance buffers behind them -- of d_scratch.
+template <bool VAR, class Params>
+int launch_levels(const Params& P, uint32_t iterations, uint32_t width, uint32_t height, const double* d_rgb,
+                  const double* d_var, const double* d_normal, const double* d_albedo, const double* d_depth,
+                  double* d_out, void* d_scratch, void* stream) {
+  const uint64_t n = (uint64_t)width * height;
+  double* const base = static_cast<double*>(d_scratch);
+  double* buf[2] = {base, base + 3 * n};
+  double* vbuf[2] = {VAR ? base + 6 * n : nullptr, VAR ? base + 7 * n : nullptr};
+  const double* in = d_rgb;
+  const double* vin = nullptr;
+  for (uint32_t l = 0; l < iterations; l++) {
+    rpdn::DnArgs a;
+    a.L = rpdn::make_level(P, l, d_normal != nullptr, d_albedo != nullptr, d_depth != nullptr);
+    const uint32_t s = (uint32_t)a.L.step;
+    a.W = width, a.H = height;
+    a.tiles_x = ((width + s - 1) / s + rpdn::TX - 1) / rpdn::TX;
+    const uint32_t tiles_y = ((height + s - 1) / s + rpdn::TY - 1) / rpdn::TY;
+    a.first = l == 0, a.last = l + 1 == iterations;
+    a.rgb = d_rgb, a.in = in;
+    a.normal = d_normal, a.albedo = d_albedo, a.depth = d_depth;
+    a.out = a.last ? d_out : buf[l & 1u];
+    a.var = d_var, a.vin = vin;
+    a.vout = VAR && !a.last ? vbuf[l & 1u] : nullptr;
+    const uint64_t grid = (uint64_t)a.tiles_x * s * tiles_y * s;  // < 2^31: at most (2048 + 128) x (8192 + 128) blocks
+    hipLaunchKernelGGL(rpdn::denoise_level<VAR>, dim3((unsigned)grid), dim3(rpdn::DN_BLOCK), 0, (hipStream_t)stream, a);
+    RP_HIP(hipGetLastError());
+    in = a.out;
+    vin = a.vout;
+  }
+  return RP_OK;
+}
+
+// rp_denoise and rp_denoise_var: the frames up, `enqueue(buffers..., stream)` timed by events, the result down.
+// var NULL: rp_denoise (scratch of 6 doubles per pixel instead of 8).
+template <class Enqueue>
+int denoise_sync(int device, uint32_t width, uint32_t height, const double* rgb, const double* var, const double* normal,
+                 const double* albedo, const double* depth, double* out, double* seconds, Enqueue enqueue) {
+  const uint64_t n = (uint64_t)width * height;
+  if (overlaps(out, 24 * n, rgb, 24 * n) || overlaps(out, 24 * n, normal, 24 * n) || overlaps(out, 24 * n, albedo, 24 * n) ||
+      overlaps(out, 24 * n, depth, 8 * n) || overlaps(out, 24 * n, var, 24 * n))
+    return fail(RP_EINVAL, "out must not alias an input");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RP_ENODEV, "no HIP device");
+  if (device < 0 || device >= count) return fail(RP_EINVAL, "device out of range");
+  DeviceGuard g(device);
+  float ms = 0.f;
+  {
+    Stream st;
+    Event e0, e1;
+    DevBuf<double> d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch;
+    if (hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking) != hipSuccess) return fail(RP_EHIP, "stream");
+    if (!d_rgb.alloc(3 * n) || !d_out.alloc(3 * n) || !d_scratch.alloc(var ? 8 * n : 6 * n) ||
+        (var && !d_var.alloc(3 * n)) || (normal && !d_normal.alloc(3 * n)) || (albedo && !d_albedo.alloc(3 * n)) ||
+        (depth && !d_depth.alloc(n)))
+      return fail(RP_ENOMEM, "hipMalloc frame buffers");
+    if (hipEventCreate(e0.put()) != hipSuccess || hipEventCreate(e1.put()) != hipSuccess) return fail(RP_EHIP, "event");
+    RP_HIP(hipMemcpy(d_rgb.get(), rgb, 24 * n, hipMemcpyHostToDevice));
+    if (var) RP_HIP(hipMemcpy(d_var.get(), var, 24 * n, hipMemcpyHostToDevice));
+    if (normal) RP_HIP(hipMemcpy(d_normal.get(), normal, 24 * n, hipMemcpyHostToDevice));
+    if (albedo) RP_HIP(hipMemcpy(d_albedo.get(), albedo, 24 * n, hipMemcpyHostToDevice));
+    if (depth) RP_HIP(hipMemcpy(d_depth.get(), depth, 8 * n, hipMemcpyHostToDevice));
+    (void)hipEventRecord(e0.get(), st.get());
+    const int rc = enqueue(d_rgb.get(), d_var.get(), d_normal.get(), d_albedo.get(), d_depth.get(), d_out.get(),
+                           d_scratch.get(), st.get());
+    if (rc) return rc;
+    (void)hipEventRecord(e1.get(), st.get());
+    const hipError_t e = hipStreamSynchronize(st.get());
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("denoise: ") + hipGetErrorString(e));
+    (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
+    RP_HIP(hipMemcpy(out, d_out.get(), 24 * n, hipMemcpyDeviceToHost));
+  }
+  if (seconds) *seconds = ms * 1e-3;
+  return RP_OK;
+}
+
+const char* const VAR_RANGE = "denoise params out of range: iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo, "
+                              "albedo_eps, sigma_var and var_eps > 0 and finite";
 
 }  // namespace
 
@@ -150,34 +263,11 @@ int rp_denoise_device(const rp_denoise_params* params, uint32_t width, uint32_t 
   if (!rpdn::resolve(params, P))
     return fail(RP_EINVAL, "denoise params out of range: iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo "
                            "and albedo_eps > 0 and finite, sigma_color finite (negative disables)");
-  const uint64_t n = (uint64_t)width * height, b3 = 3 * n * sizeof(double), b1 = n * sizeof(double);
-  if (overlaps(d_out, b3, d_rgb, b3) || overlaps(d_out, b3, d_normal, b3) || overlaps(d_out, b3, d_albedo, b3) ||
-      overlaps(d_out, b3, d_depth, b1))
-    return fail(RP_EINVAL, "out must not alias an input");
-  if (overlaps(d_scratch, 2 * b3, d_out, b3) || overlaps(d_scratch, 2 * b3, d_rgb, b3) ||
-      overlaps(d_scratch, 2 * b3, d_normal, b3) || overlaps(d_scratch, 2 * b3, d_albedo, b3) ||
-      overlaps(d_scratch, 2 * b3, d_depth, b1))
-    return fail(RP_EINVAL, "scratch must not alias an input or out");
-  if (reinterpret_cast<uintptr_t>(d_scratch) % sizeof(double)) return fail(RP_EINVAL, "scratch must be 8-byte aligned");
-  double* buf[2] = {static_cast<double*>(d_scratch), static_cast<double*>(d_scratch) + 3 * n};
-  const double* in = d_rgb;
-  for (uint32_t l = 0; l < P.iterations; l++) {
-    rpdn::DnArgs a;
-    a.L = rpdn::make_level(P, l, d_normal != nullptr, d_albedo != nullptr, d_depth != nullptr);
-    const uint32_t s = (uint32_t)a.L.step;
-    a.W = width, a.H = height;
-    a.tiles_x = ((width + s - 1) / s + rpdn::TX - 1) / rpdn::TX;
-    const uint32_t tiles_y = ((height + s - 1) / s + rpdn::TY - 1) / rpdn::TY;
-    a.first = l == 0, a.last = l + 1 == P.iterations;
-    a.rgb = d_rgb, a.in = in;
-    a.normal = d_normal, a.albedo = d_albedo, a.depth = d_depth;
-    a.out = a.last ? d_out : buf[l & 1u];
-    const uint64_t grid = (uint64_t)a.tiles_x * s * tiles_y * s;  // < 2^31: at most (2048 + 128) x (8192 + 128) blocks
-    hipLaunchKernelGGL(rpdn::denoise_level, dim3((unsigned)grid), dim3(rpdn::DN_BLOCK), 0, (hipStream_t)stream, a);
-    RP_HIP(hipGetLastError());
-    in = a.out;
-  }
-  return RP_OK;
+  if ((rc = check_buffers(width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out, d_scratch,
+                          2ull * 24 * width * height)))
+    return rc;
+  return launch_levels<false>(P, P.iterations, width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out,
+                              d_scratch, stream);
 }
 
 int rp_denoise(const rp_denoise_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
@@ -187,40 +277,56 @@ int rp_denoise(const rp_denoise_params* params, int device, uint32_t width, uint
   if (!rgb || !out) return fail(RP_EINVAL, "rgb and out must be non-NULL");
   rp_denoise_params P;
   if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, "denoise params out of range");
-  const uint64_t n = (uint64_t)width * height;
-  if (overlaps(out, 24 * n, rgb, 24 * n) || overlaps(out, 24 * n, normal, 24 * n) || overlaps(out, 24 * n, albedo, 24 * n) ||
-      overlaps(out, 24 * n, depth, 8 * n))
-    return fail(RP_EINVAL, "out must not alias an input");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RP_ENODEV, "no HIP device");
-  if (device < 0 || device >= count) return fail(RP_EINVAL, "device out of range");
-  DeviceGuard g(device);
-  float ms = 0.f;
-  {
-    Stream st;
-    Event e0, e1;
-    DevBuf<double> d_rgb, d_normal, d_albedo, d_depth, d_out, d_scratch;
-    if (hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking) != hipSuccess) return fail(RP_EHIP, "stream");
-    if (!d_rgb.alloc(3 * n) || !d_out.alloc(3 * n) || !d_scratch.alloc(6 * n) || (normal && !d_normal.alloc(3 * n)) ||
-        (albedo && !d_albedo.alloc(3 * n)) || (depth && !d_depth.alloc(n)))
-      return fail(RP_ENOMEM, "hipMalloc frame buffers");
-    if (hipEventCreate(e0.put()) != hipSuccess || hipEventCreate(e1.put()) != hipSuccess) return fail(RP_EHIP, "event");
-    RP_HIP(hipMemcpy(d_rgb.get(), rgb, 24 * n, hipMemcpyHostToDevice));
-    if (normal) RP_HIP(hipMemcpy(d_normal.get(), normal, 24 * n, hipMemcpyHostToDevice));
-    if (albedo) RP_HIP(hipMemcpy(d_albedo.get(), albedo, 24 * n, hipMemcpyHostToDevice));
-    if (depth) RP_HIP(hipMemcpy(d_depth.get(), depth, 8 * n, hipMemcpyHostToDevice));
-    (void)hipEventRecord(e0.get(), st.get());
-    if ((rc = rp_denoise_device(&P, width, height, d_rgb.get(), d_normal.get(), d_albedo.get(), d_depth.get(),
-                                d_out.get(), d_scratch.get(), st.get())))
-      return rc;
-    (void)hipEventRecord(e1.get(), st.get());
-    const hipError_t e = hipStreamSynchronize(st.get());
-    if (e != hipSuccess) return fail(RP_EHIP, std::string("denoise: ") + hipGetErrorString(e));
-    (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
-    RP_HIP(hipMemcpy(out, d_out.get(), 24 * n, hipMemcpyDeviceToHost));
-  }
-  if (seconds) *seconds = ms * 1e-3;
+  return denoise_sync(device, width, height, rgb, nullptr, normal, albedo, depth, out, seconds,
+                      [&](const double* d_rgb, const double*, const double* d_normal, const double* d_albedo,
+                          const double* d_depth, double* d_out, void* d_scratch, void* st) {
+                        return rp_denoise_device(&P, width, height, d_rgb, d_normal, d_albedo, d_depth, d_out, d_scratch, st);
+                      });
+}
+
+int rp_denoise_var_params_init(rp_denoise_var_params* p) {
+  if (!p) return fail(RP_EINVAL, "params is NULL");
+  rpdn::defaults(*p);
   return RP_OK;
+}
+
+int rp_denoise_var_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
+  int rc = check_frame(width, height);
+  if (rc) return rc;
+  if (!bytes) return fail(RP_EINVAL, "bytes is NULL");
+  *bytes = 2ull * (3ull + 1ull) * sizeof(double) * width * height;  // two colour and two variance buffers
+  return RP_OK;
+}
+
+int rp_denoise_var_device(const rp_denoise_var_params* params, uint32_t width, uint32_t height, const double* d_rgb,
+                          const double* d_var, const double* d_normal, const double* d_albedo, const double* d_depth,
+                          double* d_out, void* d_scratch, void* stream) {
+  int rc = check_frame(width, height);
+  if (rc) return rc;
+  if (!d_rgb || !d_var || !d_out || !d_scratch) return fail(RP_EINVAL, "rgb, var, out and scratch must be non-NULL");
+  rp_denoise_var_params P;
+  if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, VAR_RANGE);
+  if ((rc = check_buffers(width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch,
+                          2ull * 32 * width * height)))
+    return rc;
+  return launch_levels<true>(P, P.base.iterations, width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out,
+                             d_scratch, stream);
+}
+
+int rp_denoise_var(const rp_denoise_var_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
+                   const double* var, const double* normal, const double* albedo, const double* depth, double* out,
+                   double* seconds) {
+  int rc = check_frame(width, height);
+  if (rc) return rc;
+  if (!rgb || !var || !out) return fail(RP_EINVAL, "rgb, var and out must be non-NULL");
+  rp_denoise_var_params P;
+  if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, VAR_RANGE);
+  return denoise_sync(device, width, height, rgb, var, normal, albedo, depth, out, seconds,
+                      [&](const double* d_rgb, const double* d_var, const double* d_normal, const double* d_albedo,
+                          const double* d_depth, double* d_out, void* d_scratch, void* st) {
+                        return rp_denoise_var_device(&P, width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out,
+                                                     d_scratch, st);
+                      });
 }
 
 }  // extern "C"

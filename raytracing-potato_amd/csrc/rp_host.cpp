@@ -14,6 +14,7 @@
 
 #include "rp_bvh.h"
 #include "rp_denoise.h"
+#include "rp_variance.h"
 #include "rp_draw.h"
 #include "rp_isect.h"
 #include "rp_kernel.h"
@@ -990,26 +991,18 @@ int rph_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bo
   return RP_OK;
 }
 
+}  // extern "C"
+
 // The denoiser's levels as a plain loop over rp_denoise.h (what rp_denoise.hip's kernel does per lane): demodulate once,
 // every level from one colour buffer into the other, remodulate (or copy a pass-through pixel's rgb) at the end.
-int rph_denoise(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* rgb, const double* normal,
-                const double* albedo, const double* depth, double* out) {
-  if (width == 0 || height == 0 || width > 65535 || height > 65535)
-    return fail("rph_denoise: width and height must be 1..65535");
-  if (!rgb || !out) return fail("rph_denoise: rgb and out must be non-NULL");
-  rp_denoise_params P;
-  if (!rpdn::resolve(params, P))
-    return fail("rph_denoise: params out of range (iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo and "
-                "albedo_eps > 0 and finite, sigma_color finite)");
+// VAR (rph_denoise_var, P an rp_denoise_var_params): the variance v travels with the colour.
+template <bool VAR, class Params>
+static void denoise_loop(const Params& P, uint32_t iterations, double eps, uint32_t width, uint32_t height,
+                         const double* rgb, const double* var, const double* normal, const double* albedo,
+                         const double* depth, double* out) {
   const uint64_t n = (uint64_t)width * height;
-  auto overlaps = [&](const double* in, uint64_t channels) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(out), y = reinterpret_cast<uintptr_t>(in);
-    return in && x < y + 8 * channels * n && y < x + 24 * n;
-  };
-  if (overlaps(rgb, 3) || overlaps(normal, 3) || overlaps(albedo, 3) || overlaps(depth, 1))
-    return fail("rph_denoise: out must not alias an input");
-  std::vector<double> cur(3 * n), nxt(3 * n);
-  auto pixel = [&](const std::vector<double>& c, uint64_t i) {
+  std::vector<double> cur(3 * n), nxt(3 * n), vcur(VAR ? n : 0), vnxt(VAR ? n : 0);
+  auto pixel = [&](const std::vector<double>& c, const std::vector<double>& v, uint64_t i) {
     rpdn::Px p = {};
     p.cx = c[3 * i], p.cy = c[3 * i + 1], p.cz = c[3 * i + 2];
     if (normal) {
@@ -1018,35 +1011,97 @@ int rph_denoise(const rp_denoise_params* params, uint32_t width, uint32_t height
     }
     if (albedo) p.ax = albedo[3 * i], p.ay = albedo[3 * i + 1], p.az = albedo[3 * i + 2];
     if (depth) p.z = depth[i];
+    if (VAR) p.v = v[i];
     return p;
   };
-  for (uint64_t i = 0; i < 3 * n; i++) cur[i] = albedo ? rpdn::demod(rgb[i], albedo[i], P.albedo_eps) : rgb[i];
+  for (uint64_t i = 0; i < 3 * n; i++) cur[i] = albedo ? rpdn::demod(rgb[i], albedo[i], eps) : rgb[i];
+  if (VAR)
+    for (uint64_t i = 0; i < n; i++) {
+      double v[3];
+      for (int k = 0; k < 3; k++) v[k] = albedo ? rpdn::demod_var(var[3 * i + k], albedo[3 * i + k], eps) : var[3 * i + k];
+      vcur[i] = rpdn::sum3(v[0], v[1], v[2]);
+    }
   rpdn::Level L{};
-  for (uint32_t l = 0; l < P.iterations; l++) {
+  for (uint32_t l = 0; l < iterations; l++) {
     L = rpdn::make_level(P, l, normal != nullptr, albedo != nullptr, depth != nullptr);
     const int64_t s = L.step;
     for (uint32_t j = 0; j < height; j++)
       for (uint32_t i = 0; i < width; i++) {
         const uint64_t at = (uint64_t)j * width + i;
-        rpdn::level_step(
-            L, pixel(cur, at),
+        double ov = 0.0;
+        rpdn::level_step_v<VAR>(
+            L, pixel(cur, vcur, at),
             [&](int dx, int dy, rpdn::Px& q) {
               const int64_t qi = (int64_t)i + s * dx, qj = (int64_t)j + s * dy;
               if (qi < 0 || qi >= (int64_t)width || qj < 0 || qj >= (int64_t)height) return false;
-              q = pixel(cur, (uint64_t)qj * width + (uint64_t)qi);
+              q = pixel(cur, vcur, (uint64_t)qj * width + (uint64_t)qi);
               return true;
             },
-            nxt[3 * at], nxt[3 * at + 1], nxt[3 * at + 2]);
+            nxt[3 * at], nxt[3 * at + 1], nxt[3 * at + 2], ov);
+        if (VAR) vnxt[at] = ov;
       }
     cur.swap(nxt);
+    vcur.swap(vnxt);
   }
   for (uint64_t at = 0; at < n; at++) {
-    const rpdn::Px p = pixel(cur, at);
+    const rpdn::Px p = pixel(cur, vcur, at);
     for (int k = 0; k < 3; k++) {
       const uint64_t i = 3 * at + k;
-      out[i] = rpdn::passes(L, p) ? rgb[i] : (albedo ? rpdn::remod(cur[i], albedo[i], P.albedo_eps) : cur[i]);
+      out[i] = rpdn::passes(L, p) ? rgb[i] : (albedo ? rpdn::remod(cur[i], albedo[i], eps) : cur[i]);
     }
   }
+}
+
+// What rph_denoise and rph_denoise_var refuse about their frames (var NULL: the former); NULL = fine.
+static const char* denoise_frames(uint32_t width, uint32_t height, const double* rgb, const double* var,
+                                  const double* normal, const double* albedo, const double* depth, const double* out) {
+  if (width == 0 || height == 0 || width > 65535 || height > 65535) return "width and height must be 1..65535";
+  if (!rgb || !out) return "rgb and out must be non-NULL";
+  const uint64_t n = (uint64_t)width * height;
+  auto overlaps = [&](const double* in, uint64_t channels) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(out), y = reinterpret_cast<uintptr_t>(in);
+    return in && x < y + 8 * channels * n && y < x + 24 * n;
+  };
+  if (overlaps(rgb, 3) || overlaps(normal, 3) || overlaps(albedo, 3) || overlaps(depth, 1) || overlaps(var, 3))
+    return "out must not alias an input";
+  return nullptr;
+}
+
+extern "C" {
+
+int rph_denoise(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* rgb, const double* normal,
+                const double* albedo, const double* depth, double* out) {
+  if (const char* why = denoise_frames(width, height, rgb, nullptr, normal, albedo, depth, out))
+    return fail(std::string("rph_denoise: ") + why);
+  rp_denoise_params P;
+  if (!rpdn::resolve(params, P))
+    return fail("rph_denoise: params out of range (iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo and "
+                "albedo_eps > 0 and finite, sigma_color finite)");
+  denoise_loop<false>(P, P.iterations, P.albedo_eps, width, height, rgb, nullptr, normal, albedo, depth, out);
+  return RP_OK;
+}
+
+int rph_denoise_var(const rp_denoise_var_params* params, uint32_t width, uint32_t height, const double* rgb,
+                    const double* var, const double* normal, const double* albedo, const double* depth, double* out) {
+  if (const char* why = denoise_frames(width, height, rgb, var, normal, albedo, depth, out))
+    return fail(std::string("rph_denoise_var: ") + why);
+  if (!var) return fail("rph_denoise_var: var must be non-NULL");
+  rp_denoise_var_params P;
+  if (!rpdn::resolve(params, P))
+    return fail("rph_denoise_var: params out of range (iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo, "
+                "albedo_eps, sigma_var and var_eps > 0 and finite)");
+  denoise_loop<true>(P, P.base.iterations, P.base.albedo_eps, width, height, rgb, var, normal, albedo, depth, out);
+  return RP_OK;
+}
+
+// rp_variance.h's batch_variance per pixel and channel: what rp_variance.hip's kernel does per lane.
+int rph_batch_variance(uint32_t spp, uint32_t samples_per_stream, uint64_t n_pixels, const double* sums, double* var) {
+  if (!sums || !var) return fail("rph_batch_variance: sums and var must be non-NULL");
+  const uint32_t sps = samples_per_stream ? samples_per_stream : RP_SAMPLES_PER_STREAM;
+  const uint32_t B = rpv::batches(spp, sps);
+  if (B < 2) return fail("rph_batch_variance: needs at least two sample batches per pixel (spp > samples_per_stream)");
+  for (uint64_t i = 0; i < n_pixels; i++)
+    for (uint32_t c = 0; c < 3; c++) var[3 * i + c] = rpv::batch_variance(sums + 3 * i * B + c, 3, B, spp, sps);
   return RP_OK;
 }
 

@@ -261,31 +261,56 @@ class DeviceScene:
         F.check(F.rp().rp_render_aov_device_ws(self.handle, workspace.handle if workspace else None, ctypes.byref(cam),
                                                ctypes.byref(p), *ptr, ctypes.c_void_p(s.cuda_stream)))
 
+    # ---- per-pixel variance from the batch sums (rp_render_variance_device_ws) -------------------------
+    def render_variance_device(self, params: RenderParams, var, workspace: "Workspace | None" = None,
+                               stream=None) -> None:
+        """rp_render_variance_device_ws: the variance of every pixel's mean, from the batch sums the last render of
+        `params` left in `workspace` (None = the scene's), into `var` (torch f64, >= 3 * shard_slot_count elements,
+        compact shard order like the render's rgb) on `stream` (torch stream; default: current).  Needs more than one
+        sample batch per pixel (spp > samples_per_stream); order it after that render and before the workspace's next."""
+        import torch
+        assert var.dtype == torch.float64 and var.is_cuda and var.is_contiguous()
+        assert var.numel() >= 3 * shard_slot_count(params)
+        if workspace is not None:
+            assert workspace.scene is self and workspace.handle
+        s = stream if stream is not None else torch.cuda.current_stream(var.device)
+        p = params.to_c()
+        F.check(F.rp().rp_render_variance_device_ws(self.handle, workspace.handle if workspace else None,
+                                                    ctypes.byref(p), var.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+
     # ---- beauty + guides + denoiser, device-resident ---------------------------------------------------
-    def render_denoised(self, params: RenderParams, denoise=None, bgra: bool = False, camera=None, stream=None):
+    def render_denoised(self, params: RenderParams, denoise=None, bgra: bool = False, camera=None, stream=None,
+                        variance: bool = False):
         """A denoised frame without a host round trip: the beauty render and the feature pass into shard buffers,
         rp_frame_assemble at num_shards = 1 into frame order, then rp_denoise_device (`denoise`: rp_denoise_params, a
         dict of its fields or None = the defaults), all on `stream` (torch stream; default: current).  Returns the frame
         as a torch f64 tensor (h, w, 3) on the scene's device and, with bgra=True, also its to_srgb_u8 bytes (h, w, 4)
         uint8 in TGA order B, G, R, A (rp_shard_to_bgra8: a frame-order buffer is the shard buffer of the frame tiled
         tile_w = width, tile_h = height).  One device holds the whole frame (multi-GPU frames assemble with
-        rp_frame_assemble_ws and denoise_device)."""
+        rp_frame_assemble_ws and denoise_device).  variance=True: the variance pass (render_variance_device) follows the
+        beauty render and the filter is the variance-guided one (rp_denoise_var_device; `denoise`: as
+        denoise_var_params takes it); `params` must give more than one sample batch per pixel."""
         import torch
         from dataclasses import replace
         if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
             raise ValueError("render_denoised renders the whole frame on one device (num_shards = 1, interleave)")
+        if variance and params.spp <= (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM):
+            raise ValueError("render_denoised(variance=True) needs at least two sample batches per pixel "
+                             f"(spp > samples_per_stream): spp = {params.spp}, samples_per_stream = "
+                             f"{params.samples_per_stream or F.RP_SAMPLES_PER_STREAM}")
         dev = torch.device("cuda", self.device)
         s = stream if stream is not None else torch.cuda.current_stream(dev)
         w, h, n = params.width, params.height, shard_slot_count(params)
         self.reserve(params)
         with torch.cuda.stream(s):
-            shard = {k: torch.empty(c * n, dtype=torch.float64, device=dev)
-                     for k, c in (("rgb", 3), ("normal", 3), ("albedo", 3), ("depth", 1))}
-            frame = {k: torch.empty(c * w * h, dtype=torch.float64, device=dev)
-                     for k, c in (("rgb", 3), ("normal", 3), ("albedo", 3), ("depth", 1))}
+            bufs = (("rgb", 3), ("normal", 3), ("albedo", 3), ("depth", 1)) + ((("var", 3),) if variance else ())
+            shard = {k: torch.empty(c * n, dtype=torch.float64, device=dev) for k, c in bufs}
+            frame = {k: torch.empty(c * w * h, dtype=torch.float64, device=dev) for k, c in bufs}
             ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
             out = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
             self.render_device(params, shard["rgb"], ctr, camera=camera, stream=s)
+            if variance:
+                self.render_variance_device(params, shard["var"], stream=s)
             self.render_aov_device(params, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
                                    camera=camera, stream=s)
             p = params.to_c()
@@ -293,7 +318,7 @@ class DeviceScene:
                 F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 2 * (t.numel() // n),
                                                  frame[k].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
             denoise_device(frame["rgb"], frame["normal"], frame["albedo"], frame["depth"], out, params=denoise,
-                           stream=s)
+                           stream=s, variance=frame.get("var"))
             if not bgra:
                 return out
             bytes_ = torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
@@ -548,65 +573,132 @@ def denoise_scratch_bytes(width: int, height: int) -> int:
     return b.value
 
 
-def _host_frames(rgb, normal, albedo, depth):
+def denoise_var_params(params=None, **kw) -> F.rp_denoise_var_params:
+    """rp_denoise_var_params: `params` (an rp_denoise_var_params, an rp_denoise_params taken as its base, a dict or
+    None) with fields overridden by keyword; sigma_var and var_eps beside the base's fields, all at one level.  Fields
+    left at zero take the library's defaults (sigma_var 3.0, var_eps 1e-6, the base as denoise_params; base.sigma_color
+    is ignored)."""
+    p = F.rp_denoise_var_params()
+    if isinstance(params, F.rp_denoise_var_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    elif isinstance(params, F.rp_denoise_params):
+        ctypes.memmove(ctypes.byref(p.base), ctypes.byref(params), ctypes.sizeof(params))
+    elif params:
+        kw = {**params, **kw}
+    for k, v in kw.items():
+        if k in ("sigma_var", "var_eps"):
+            setattr(p, k, v)
+        elif hasattr(p.base, k):
+            setattr(p.base, k, v)
+        else:
+            raise KeyError(f"unknown denoise parameter {k!r}")
+    return p
+
+
+def denoise_var_defaults() -> F.rp_denoise_var_params:
+    """rp_denoise_var_params_init: every field at its default (host only)."""
+    p = F.rp_denoise_var_params()
+    F.check(F.rp().rp_denoise_var_params_init(ctypes.byref(p)))
+    return p
+
+
+def denoise_var_scratch_bytes(width: int, height: int) -> int:
+    """rp_denoise_var_scratch_bytes: device bytes denoise_device(variance=...) needs beside its buffers (host only)."""
+    b = ctypes.c_uint64()
+    F.check(F.rp().rp_denoise_var_scratch_bytes(width, height, ctypes.byref(b)))
+    return b.value
+
+
+def _host_frames(rgb, normal, albedo, depth, variance=None):
     rgb = np.ascontiguousarray(rgb, dtype=np.float64)
     assert rgb.ndim == 3 and rgb.shape[2] == 3, "rgb: (h, w, 3)"
     h, w = rgb.shape[:2]
     guides = []
-    for name, g, shape in (("normal", normal, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("depth", depth, (h, w))):
+    for name, g, shape in (("normal", normal, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("depth", depth, (h, w)),
+                           ("variance", variance, (h, w, 3))):
         if g is not None:
             g = np.ascontiguousarray(g, dtype=np.float64)
             assert g.shape == shape, f"{name}: {shape}, got {g.shape}"
         guides.append(g)
-    return rgb, guides, h, w
+    return rgb, guides[:3], h, w, guides[3]
 
 
-def denoise(rgb, normal=None, albedo=None, depth=None, params=None, device: int = 0):
+def denoise(rgb, normal=None, albedo=None, depth=None, params=None, device: int = 0, variance=None):
     """rp_denoise on host arrays in frame order -- rgb, normal, albedo (h, w, 3), depth (h, w), each guide optional --
-    through the device kernel: (denoised (h, w, 3) f64, device seconds of the levels)."""
-    rgb, guides, h, w = _host_frames(rgb, normal, albedo, depth)
-    p = denoise_params(params)
+    through the device kernel: (denoised (h, w, 3) f64, device seconds of the levels).  variance (h, w, 3): the
+    variance-guided filter (rp_denoise_var; params as denoise_var_params takes them)."""
+    rgb, guides, h, w, var = _host_frames(rgb, normal, albedo, depth, variance)
     out = np.empty_like(rgb)
     sec = ctypes.c_double()
-    F.check(F.rp().rp_denoise(ctypes.byref(p), device, w, h, rgb.ctypes.data,
-                              *[g.ctypes.data if g is not None else None for g in guides], out.ctypes.data,
-                              ctypes.byref(sec)))
+    gp = [g.ctypes.data if g is not None else None for g in guides]
+    if var is None:
+        p = denoise_params(params)
+        F.check(F.rp().rp_denoise(ctypes.byref(p), device, w, h, rgb.ctypes.data, *gp, out.ctypes.data,
+                                  ctypes.byref(sec)))
+    else:
+        p = denoise_var_params(params)
+        F.check(F.rp().rp_denoise_var(ctypes.byref(p), device, w, h, rgb.ctypes.data, var.ctypes.data, *gp,
+                                      out.ctypes.data, ctypes.byref(sec)))
     return out, sec.value
 
 
-def denoise_host(rgb, normal=None, albedo=None, depth=None, params=None) -> np.ndarray:
-    """rph_denoise: the same filter on the CPU (librp_host.so; the same arithmetic header as the kernel, equal bits)."""
-    rgb, guides, h, w = _host_frames(rgb, normal, albedo, depth)
-    p = denoise_params(params)
+def denoise_host(rgb, normal=None, albedo=None, depth=None, params=None, variance=None) -> np.ndarray:
+    """rph_denoise: the same filter on the CPU (librp_host.so; the same arithmetic header as the kernel, equal bits).
+    variance (h, w, 3): rph_denoise_var, the variance-guided filter."""
+    rgb, guides, h, w, var = _host_frames(rgb, normal, albedo, depth, variance)
     out = np.empty_like(rgb)
-    F.check_host(F.host().rph_denoise(ctypes.byref(p), w, h, rgb.ctypes.data,
-                                      *[g.ctypes.data if g is not None else None for g in guides], out.ctypes.data))
+    gp = [g.ctypes.data if g is not None else None for g in guides]
+    if var is None:
+        p = denoise_params(params)
+        F.check_host(F.host().rph_denoise(ctypes.byref(p), w, h, rgb.ctypes.data, *gp, out.ctypes.data))
+    else:
+        p = denoise_var_params(params)
+        F.check_host(F.host().rph_denoise_var(ctypes.byref(p), w, h, rgb.ctypes.data, var.ctypes.data, *gp,
+                                              out.ctypes.data))
     return out
 
 
-def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, stream=None) -> None:
+def batch_variance_host(sums, spp: int, samples_per_stream: int = 0) -> np.ndarray:
+    """rph_batch_variance: the variance pass's arithmetic on the CPU.  sums (..., B, 3): every pixel's batch sums,
+    B = ceil(spp / samples_per_stream); returns (..., 3)."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    sps = samples_per_stream or F.RP_SAMPLES_PER_STREAM
+    assert sums.ndim >= 2 and sums.shape[-1] == 3 and sums.shape[-2] == (spp + sps - 1) // sps, sums.shape
+    var = np.empty(sums.shape[:-2] + (3,), dtype=np.float64)
+    F.check_host(F.host().rph_batch_variance(spp, samples_per_stream, var.size // 3, sums.ctypes.data, var.ctypes.data))
+    return var
+
+
+def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, stream=None, variance=None) -> None:
     """rp_denoise_device on torch tensors of one device, asynchronously on `stream` (torch stream; default: current):
     rgb (h, w, 3) f64 and the optional guides normal, albedo (h, w, 3), depth (h, w) in frame order (flat tensors of
     the same sizes are taken with `out`'s shape), `out` (h, w, 3) f64, which must not alias an input.  scratch: a
-    tensor of >= denoise_scratch_bytes(w, h) bytes (default: allocated here on `stream`)."""
+    tensor of >= denoise_scratch_bytes(w, h) bytes (default: allocated here on `stream`).  variance (h, w, 3) f64:
+    rp_denoise_var_device, the variance-guided filter (params as denoise_var_params takes them, scratch of
+    denoise_var_scratch_bytes(w, h) bytes)."""
     import torch
     assert out.dtype == torch.float64 and out.is_cuda and out.is_contiguous() and out.dim() == 3 and out.shape[2] == 3
     h, w = out.shape[:2]
-    for t, m in ((rgb, 3 * w * h), (normal, 3 * w * h), (albedo, 3 * w * h), (depth, w * h)):
+    for t, m in ((rgb, 3 * w * h), (normal, 3 * w * h), (albedo, 3 * w * h), (depth, w * h), (variance, 3 * w * h)):
         if t is not None:
             assert t.dtype == torch.float64 and t.device == out.device and t.is_contiguous() and t.numel() == m
     assert rgb is not None
     s = stream if stream is not None else torch.cuda.current_stream(out.device)
-    need = denoise_scratch_bytes(w, h)
+    need = denoise_scratch_bytes(w, h) if variance is None else denoise_var_scratch_bytes(w, h)
     if scratch is None:
         with torch.cuda.stream(s):
             scratch = torch.empty(need // 8, dtype=torch.float64, device=out.device)
     assert scratch.is_cuda and scratch.device == out.device and scratch.numel() * scratch.element_size() >= need
-    p = denoise_params(params)
+    gp = [t.data_ptr() if t is not None else None for t in (normal, albedo, depth)]
     with torch.cuda.device(out.device):
-        F.check(F.rp().rp_denoise_device(ctypes.byref(p), w, h, rgb.data_ptr(),
-                                         *[t.data_ptr() if t is not None else None for t in (normal, albedo, depth)],
-                                         out.data_ptr(), scratch.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+        if variance is None:
+            p = denoise_params(params)
+            F.check(F.rp().rp_denoise_device(ctypes.byref(p), w, h, rgb.data_ptr(), *gp, out.data_ptr(),
+                                             scratch.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+        else:
+            p = denoise_var_params(params)
+            F.check(F.rp().rp_denoise_var_device(ctypes.byref(p), w, h, rgb.data_ptr(), variance.data_ptr(), *gp,
+                                                 out.data_ptr(), scratch.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
 
 
 def tga_bytes(width: int, height: int, bgra) -> bytes:

@@ -338,6 +338,30 @@ static void check_denoise() {
   p.iterations = 9;
   CHECK(rph_denoise(&p, W, H, rgb.data(), nrm.data(), alb.data(), dep.data(), out.data()) == RP_EINVAL);
   std::printf("denoise: 7 x 5 at five levels, misses passed through, aliasing and a bad level count refused\n");
+  // the variance pass's and the variance-guided filter's host loops (csrc/rp_variance.h rph_batch_variance,
+  // rph_denoise_var) on the same frame: spp 10 in batches of 4, 4 and 2, some variances zero
+  const uint32_t B = 3;
+  std::vector<double> sums(3 * B * W * H), var(3 * W * H);
+  for (uint32_t i = 0; i < W * H; i++)
+    for (uint32_t b = 0; b < B; b++)
+      for (int k = 0; k < 3; k++)
+        sums[3 * (i * B + b) + k] = (b == 2 ? 2.0 : 4.0) * rgb[3 * i + k] * (i % 4 ? 1.0 + 0.1 * b : 1.0);
+  CHECK(rph_batch_variance(10, 4, W * H, sums.data(), var.data()) == RP_OK);
+  for (uint32_t i = 0; i < 3 * W * H; i++) CHECK(var[i] >= 0.0 && var[i] < 1.0 && (i / 3 % 4 ? var[i] > 0.0 : var[i] < 1e-30));
+  CHECK(rph_batch_variance(4, 4, W * H, sums.data(), var.data()) == RP_EINVAL);
+  rp_denoise_var_params v{};
+  v.base.iterations = 5;
+  CHECK(rph_denoise_var(&v, W, H, rgb.data(), var.data(), nrm.data(), alb.data(), dep.data(), out.data()) == RP_OK);
+  for (uint32_t i : {3u, 17u})
+    for (int k = 0; k < 3; k++) CHECK(out[3 * i + k] == rgb[3 * i + k]);
+  for (double x : out) CHECK(x > 0.0 && x < 1.0);
+  CHECK(rph_denoise_var(nullptr, W, H, rgb.data(), var.data(), nullptr, nullptr, nullptr, out2.data()) == RP_OK);
+  CHECK(rph_denoise_var(&v, W, H, rgb.data(), var.data(), nrm.data(), alb.data(), dep.data(), var.data()) == RP_EINVAL);
+  CHECK(rph_denoise_var(&v, W, H, rgb.data(), nullptr, nrm.data(), alb.data(), dep.data(), out.data()) == RP_EINVAL);
+  v.sigma_var = -1.0;
+  CHECK(rph_denoise_var(&v, W, H, rgb.data(), var.data(), nrm.data(), alb.data(), dep.data(), out.data()) == RP_EINVAL);
+  std::printf("variance: batches of 4, 4 and 2; variance-guided denoise: misses passed through, aliasing, a missing\n"
+              "variance and a negative sigma_var refused\n");
 }
 
 int main(int argc, char** argv) {
