@@ -518,7 +518,7 @@ int rp_denoise(const rp_denoise_params* params, int device, uint32_t width, uint
  * shard_map are honoured: a balanced shard uses the plan the beauty render left in the workspace, as rp_render_aov does.
  * RP_EINVAL: B < 2 (nothing to take a spread of), a workspace whose batch reservation (rp_workspace_reserve) does not
  * cover the shard's slots x B, a balanced shard without a plan, NULL d_shard_var.  The sums of a multi-frame launch
- * (rp_render_frames_device_ws) are not supported.
+ * (rp_render_frames_device_ws) are not supported: rp_accum_frames_device takes the variance over such a launch's frames.
  * The shard buffer is laid out like the render's rgb: gathered shards assemble with rp_frame_assemble[_ws] at
  * words_per_slot = 6, and rp_shard_unpack[_map] unpacks it with channels = 3. */
 int rp_render_variance_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_render_params* params,
@@ -558,6 +558,62 @@ int rp_denoise_var_device(const rp_denoise_var_params* params, uint32_t width, u
 int rp_denoise_var(const rp_denoise_var_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
                    const double* var, const double* normal, const double* albedo, const double* depth, double* out,
                    double* seconds);
+
+/* Progressive rendering: the frames of successive launches folded, on the device, into a running mean and the variance
+ * of that mean, and the count of pixels whose error is still above a tolerance -- the stopping rule.  Frame f of
+ * rp_render_frames_device_ws is the frame of seed + f*B*W*H (B = ceil(spp / samples_per_stream)), so the n frames of a
+ * launch are n independent estimates of every pixel and the next launch at seed + n*B*W*H continues them without
+ * repeating a stream: the one-stream-per-pixel fast path gets a variance, with n - 1 degrees of freedom, that
+ * rp_render_variance_device_ws cannot give it.  DESIGN.md 4.13.
+ *   Definition.  A word is one double of a buffer, whatever it holds.  Its state is (mean, m2); frame number k counts
+ *   from 1 over all frames ever folded in.  In IEEE binary64, in the order written and without contraction:
+ *     r_k  = 1.0 / (double)k
+ *     d    = x - mean
+ *     mean = mean + d * r_k
+ *     m2   = m2 + d * (x - mean)            -- the new mean
+ *   (Welford 1962).  With n_prior = 0 the state is not read: it starts at mean = 0.0, m2 = 0.0 and k at 1, hence after
+ *   one frame mean == x bit for bit and m2 == 0.  After n >= 2 frames the variance of the mean is
+ *     var = m2 / ((double)n * (double)(n - 1))
+ *   NaN and infinities propagate.
+ * rp_accum_frames_device is purely elementwise: it knows nothing of scenes, shards or channels, and serves compact shard
+ * buffers (slots outside the frame just carry their garbage along), full frames, rgb or anything else laid out as
+ * n_frames blocks.  d_frames: frame f's n_words doubles at f * frame_stride (in doubles, >= n_words); they are folded in
+ * the order f = 0 .. n_frames - 1 into (d_mean, d_m2), n_words doubles each, which already hold n_prior frames (0: they
+ * are only written).  d_var (nullable): n_words doubles, the variance of the mean for n = n_prior + n_frames.
+ * Asynchronous on `stream` on the CURRENT device (as rp_frame_assemble); one kernel launch, no allocation and no
+ * synchronisation (capturable, like rp_render_device).  Any n_words >= 1, stride and alignment are served; 16-byte
+ * aligned buffers with an even stride take the wide path.  RP_EINVAL: NULL d_frames, d_mean or d_m2; n_words or n_frames
+ * of zero; frame_stride < n_words; d_var with n < 2; n above 2^31 - 1; n_words above 2^40 - 512; an output that aliases
+ * the frames or another output. */
+int rp_accum_frames_device(uint64_t n_words, uint32_t n_prior, uint32_t n_frames, const double* d_frames,
+                           uint64_t frame_stride, double* d_mean, double* d_m2, double* d_var, void* stream);
+
+/* The error measure of a pixel, from the three words of its mean m and the three of its variance v:
+ *     s  = (v.r + v.g) + v.b
+ *     q  = ((m.r*m.r + m.g*m.g) + m.b*m.b) + eps
+ *     e2 = s / q
+ *   the squared relative standard error; eps makes it an absolute error for dark pixels.  A pixel is "over" when
+ *   e2 > tol*tol.  A zero field takes its default (tol 0.05, eps 1e-4), params = NULL means both; tol must be > 0 and eps
+ *   > 0 and finite.
+ * rp_accum_error_device_ws: d_shard_mean and d_shard_var are compact shard buffers of `params`' shard, 3 doubles per slot
+ * (the render's shard order, as rp_render_variance_device_ws writes them); slots of edge tiles outside the frame are
+ * never read or counted.  d_stats (RP_ERROR_STATS_LEN uint64, 8-byte aligned) is zeroed on `stream`, then receives
+ *     [0] the pixels counted              [1] the pixels over
+ *     [2] the bit pattern of the largest finite e2 (of the positive ones; 0 when there is none)
+ *     [3] the pixels whose e2 is not finite (NaN: never over; +inf: also over)
+ * All four are order-free -- integer sums and an integer maximum of positive doubles' bits -- so the result is exact and
+ * the same on every run.  Shards add up: pixels, over and non-finite sum over the shards of a frame, the maximum is the
+ * maximum of theirs.  params.shard, num_shards, tile_w, tile_h and shard_map are honoured; a balanced shard uses the plan
+ * the beauty render left in the workspace (NULL = the scene's).  Asynchronous on `stream`, never allocates or
+ * synchronises (capturable): one small launch that clears d_stats and the pass's own; an empty shard leaves the zeros.  RP_EINVAL: a
+ * NULL buffer, parameters out of range, a balanced shard without a plan. */
+#define RP_ERROR_STATS_LEN 4
+typedef struct rp_error_params {
+  double tol, eps;
+} rp_error_params;
+int rp_accum_error_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_render_params* params,
+                             const rp_error_params* error, const double* d_shard_mean, const double* d_shard_var,
+                             uint64_t* d_stats, void* stream);
 
 /* Output stage on the device: the reference's to_srgb_u8 (utility.rs:212-220, alpha 255) of every slot of
  * a compact shard buffer, bytes in tga::save's pixel order B, G, R, A (image.rs:116-137), so a gathered

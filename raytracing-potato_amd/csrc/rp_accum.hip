@@ -1,0 +1,264 @@
+// rp_accum.hip -- progressive accumulation (include/rp.h rp_accum_frames_device and rp_accum_error_device_ws,
+// DESIGN.md 4.13): the frames of multi-frame launches folded into a running mean and the variance of that mean, and the
+// count of pixels whose relative standard error is still above a tolerance.  No ray is traced.  The arithmetic is
+// rp_accum.h's, shared with the CPU loops behind rph_accum_frames and rph_accum_error; this file is the two kernels,
+// their launches and the C-ABI.
+//
+// A translation unit of its own, linked into librp.so and librp_diag.so and, like rp_aov.hip, rp_denoise.hip and
+// rp_variance.hip, not part of the rp_build_id hash: it runs after the render and decides no ray of it.
+//
+// accum_kernel: a streaming reduction over frames.  One lane owns two consecutive words and moves them with 16-byte
+// loads and stores when every pointer is 16-byte aligned and the frame stride is even; otherwise, and for an odd last
+// word, it walks its words one by one.  The loads of ACC_GROUP frames are issued before the Welford chain that consumes
+// them in frame order; 1 / k is one division per frame, the same in every lane.  The grid is ceil(n_words / 2) lanes.
+// error_kernel: a lane per shard slot, several slots per lane above 2048 blocks (rp_units.h slot_pixel's decode, as
+// rp_variance.hip); the four statistics are
+// reduced in the wave, then in the block through LDS, then one vector atomic per block and statistic -- integer sums and
+// an integer maximum, so the result does not depend on the order of arrival.  zero_stats_kernel clears them first.
+#include "rp_state.h"  // first: the HIP runtime defines the qualifiers the shared headers use
+
+#include "rp_accum.h"
+#include "rp_units.h"
+
+#pragma clang fp contract(off)
+
+namespace rpa {
+
+constexpr int ACC_BLOCK = 256;
+constexpr int ACC_GROUP = 4;  // frames whose loads are in flight together: 4 x 16 B per lane
+constexpr int ERR_BLOCK = 256;
+constexpr int ERR_WAVES = ERR_BLOCK / 64;
+constexpr uint64_t ERR_GRID_MAX = 2048;  // 256 CUs x 8 blocks: above it a block takes several slots per lane, so the
+                                         // atomics on the four statistics words stay at 2048 per word
+
+struct AccArgs {
+  uint64_t n_words, stride;
+  uint32_t n_prior, n_frames;
+  uint32_t vec;  // every pointer 16-byte aligned and the stride even: a lane's two words move as one
+  const double* frames;
+  double* mean;
+  double* m2;
+  double* var;  // NULL: not wanted
+};
+
+template <int W>
+struct Words {
+  double v[W];
+};
+template <int W>
+__device__ __forceinline__ Words<W> load(const double* p);
+template <>
+__device__ __forceinline__ Words<1> load<1>(const double* p) {
+  return {{*p}};
+}
+template <>
+__device__ __forceinline__ Words<2> load<2>(const double* p) {
+  const double2 t = *reinterpret_cast<const double2*>(p);
+  return {{t.x, t.y}};
+}
+__device__ __forceinline__ void store(double* p, const Words<1>& w) { *p = w.v[0]; }
+__device__ __forceinline__ void store(double* p, const Words<2>& w) {
+  *reinterpret_cast<double2*>(p) = make_double2(w.v[0], w.v[1]);
+}
+
+// Words w .. w + W - 1 through every frame of the call, in frame order.
+template <int W>
+__device__ __forceinline__ void fold(const AccArgs& A, uint64_t w) {
+  Words<W> mean, m2;
+  if (A.n_prior) {
+    mean = load<W>(A.mean + w);
+    m2 = load<W>(A.m2 + w);
+  } else {
+#pragma unroll
+    for (int c = 0; c < W; c++) mean.v[c] = 0.0, m2.v[c] = 0.0;
+  }
+  const double* src = A.frames + w;
+  uint32_t k = A.n_prior;  // frames folded in so far
+  uint32_t f = 0;
+  for (; f + ACC_GROUP <= A.n_frames; f += ACC_GROUP) {
+    Words<W> x[ACC_GROUP];
+#pragma unroll
+    for (int u = 0; u < ACC_GROUP; u++) x[u] = load<W>(src + (uint64_t)(f + u) * A.stride);
+#pragma unroll
+    for (int u = 0; u < ACC_GROUP; u++) {
+      const double r = frame_weight(++k);
+#pragma unroll
+      for (int c = 0; c < W; c++) welford(x[u].v[c], r, mean.v[c], m2.v[c]);
+    }
+  }
+  for (; f < A.n_frames; f++) {
+    const Words<W> x = load<W>(src + (uint64_t)f * A.stride);
+    const double r = frame_weight(++k);
+#pragma unroll
+    for (int c = 0; c < W; c++) welford(x.v[c], r, mean.v[c], m2.v[c]);
+  }
+  store(A.mean + w, mean);
+  store(A.m2 + w, m2);
+  if (A.var) {
+    const double nn = mean_divisor(k);
+    Words<W> var;
+#pragma unroll
+    for (int c = 0; c < W; c++) var.v[c] = mean_variance(m2.v[c], nn);
+    store(A.var + w, var);
+  }
+}
+
+__global__ void __launch_bounds__(ACC_BLOCK) accum_kernel(const AccArgs A) {
+  const uint64_t w = 2 * ((uint64_t)blockIdx.x * ACC_BLOCK + threadIdx.x);
+  if (w >= A.n_words) return;
+  if (A.vec && w + 1 < A.n_words) {
+    fold<2>(A, w);
+  } else {
+    fold<1>(A, w);
+    if (w + 1 < A.n_words) fold<1>(A, w + 1);
+  }
+}
+
+// the fields slot_pixel reads, under KParams' names, and the pass's own
+struct ErrArgs {
+  uint32_t W, H, tw, th, shard, nshards, tiles_x;
+  uint64_t n_slots;
+  const uint32_t* tile_map;  // the balanced plan's deal order (NULL = interleave)
+  const double* mean;        // 3 per slot
+  const double* var;         // 3 per slot
+  double tol2, eps;
+  unsigned long long* stats;  // STATS_LEN
+};
+
+// The statistics start at zero: a kernel of its own ahead of error_kernel on the stream, not a memset -- a captured
+// graph replays a kernel node with the arguments it was captured with.
+__global__ void __launch_bounds__(64) zero_stats_kernel(unsigned long long* stats) {
+  if (threadIdx.x < STATS_LEN) stats[threadIdx.x] = 0;
+}
+
+__global__ void __launch_bounds__(ERR_BLOCK) error_kernel(const ErrArgs A) {
+  __shared__ unsigned long long part[ERR_WAVES][STATS_LEN];
+  unsigned long long n_counted = 0, n_over = 0, n_nonfinite = 0, bits = 0;
+  // a block walks the slots in steps of the grid (the same trip count for all its lanes: the ballots and the barrier
+  // below are reached by every lane); the counts are the wave's, the same in all its lanes
+  for (uint64_t base = (uint64_t)blockIdx.x * ERR_BLOCK; base < A.n_slots; base += (uint64_t)gridDim.x * ERR_BLOCK) {
+    const uint64_t slot = base + threadIdx.x;
+    bool counted = false, over = false, nonfinite = false;
+    uint32_t pi, pj;
+    if (slot < A.n_slots && rpk::slot_pixel(A, slot, pi, pj)) {
+      const double e2 = error2(A.mean + 3 * slot, A.var + 3 * slot, A.eps);
+      counted = true;
+      over = e2 > A.tol2;
+      if (!finite(e2)) {
+        nonfinite = true;
+      } else if (e2 > 0.0) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(e2);
+        bits = b > bits ? b : bits;
+      }
+    }
+    n_counted += __popcll(__ballot(counted));
+    n_over += __popcll(__ballot(over));
+    n_nonfinite += __popcll(__ballot(nonfinite));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long other = __shfl_down(bits, off);
+    bits = other > bits ? other : bits;
+  }
+  const uint32_t wave = threadIdx.x / 64;
+  if (threadIdx.x % 64 == 0) {
+    part[wave][STAT_PIXELS] = n_counted;
+    part[wave][STAT_OVER] = n_over;
+    part[wave][STAT_MAX_BITS] = bits;
+    part[wave][STAT_NONFINITE] = n_nonfinite;
+  }
+  __syncthreads();
+  if (threadIdx.x < STATS_LEN) {
+    const uint32_t s = threadIdx.x;
+    unsigned long long v = part[0][s];
+#pragma unroll
+    for (int i = 1; i < ERR_WAVES; i++) {
+      const unsigned long long o = part[i][s];
+      v = s == STAT_MAX_BITS ? (o > v ? o : v) : v + o;
+    }
+    if (v) {
+      if (s == STAT_MAX_BITS)
+        atomicMax(A.stats + s, v);
+      else
+        atomicAdd(A.stats + s, v);
+    }
+  }
+}
+
+static bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
+  if (!a || !b) return false;
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+
+}  // namespace rpa
+
+extern "C" {
+
+int rp_accum_frames_device(uint64_t n_words, uint32_t n_prior, uint32_t n_frames, const double* d_frames,
+                           uint64_t frame_stride, double* d_mean, double* d_m2, double* d_var, void* stream) {
+  if (!d_frames || !d_mean || !d_m2) return fail(RP_EINVAL, "d_frames, d_mean and d_m2 must be non-NULL");
+  if (n_words == 0) return fail(RP_EINVAL, "n_words is zero");
+  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
+  if (frame_stride < n_words) return fail(RP_EINVAL, "frame_stride is below n_words: the frames would overlap");
+  const uint64_t n = (uint64_t)n_prior + n_frames;
+  if (n > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames (n_prior + n_frames)");
+  if (d_var && n < 2) return fail(RP_EINVAL, "the variance needs at least two frames (n_prior + n_frames >= 2)");
+  const uint64_t lanes = (n_words + 1) / 2, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
+  if (grid > 0x7fffffffu) return fail(RP_EINVAL, "n_words is above 2^40 - 512: more than 2^31 - 1 blocks");
+  // byte counts: n_words < 2^40 here; a stride that wraps 64 bits is the caller's address space running out
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_words;
+  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
+    if (rpa::overlaps(o, out_bytes, d_frames, in_bytes))
+      return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias the frames");
+  if (rpa::overlaps(d_mean, out_bytes, d_m2, out_bytes) || rpa::overlaps(d_var, out_bytes, d_mean, out_bytes) ||
+      rpa::overlaps(d_var, out_bytes, d_m2, out_bytes))
+    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
+  rpa::AccArgs a;
+  a.n_words = n_words, a.stride = frame_stride;
+  a.n_prior = n_prior, a.n_frames = n_frames;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(d_frames) | reinterpret_cast<uintptr_t>(d_mean) |
+                         reinterpret_cast<uintptr_t>(d_m2) | reinterpret_cast<uintptr_t>(d_var);
+  a.vec = bits % 16 == 0 && frame_stride % 2 == 0;
+  a.frames = d_frames, a.mean = d_mean, a.m2 = d_m2, a.var = d_var;
+  hipLaunchKernelGGL(rpa::accum_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, a);
+  RP_HIP(hipGetLastError());
+  return RP_OK;
+}
+
+int rp_accum_error_device_ws(rp_scene* s, rp_workspace* w, const rp_render_params* p, const rp_error_params* e,
+                             const double* d_shard_mean, const double* d_shard_var, uint64_t* d_stats, void* stream) {
+  int rc = use_ws(s, w);
+  if (rc) return rc;
+  if (!d_shard_mean || !d_shard_var || !d_stats)
+    return fail(RP_EINVAL, "d_shard_mean, d_shard_var and d_stats must be non-NULL");
+  double tol, eps;
+  if (!rpa::resolve(e, tol, eps))
+    return fail(RP_EINVAL, "error params out of range (tol > 0; eps > 0 and finite)");
+  Tiling t;
+  if ((rc = frame_tiling(p, t))) return rc;
+  // a balanced shard holds the tiles of the beauty shard rendered before it: the plan that render left in the workspace
+  if (t.balanced && !w->plan_matches(p, t))
+    return fail(RP_EINVAL, "no balanced plan for this frame in the workspace: render it first");
+  DeviceGuard g(s->device);
+  static_assert(RP_ERROR_STATS_LEN == rpa::STATS_LEN, "include/rp.h and rp_accum.h disagree");
+  hipLaunchKernelGGL(rpa::zero_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                     reinterpret_cast<unsigned long long*>(d_stats));
+  RP_HIP(hipGetLastError());
+  if (t.n_slots == 0) return RP_OK;
+  rpa::ErrArgs a;
+  a.W = p->width, a.H = p->height, a.tw = t.tw, a.th = t.th, a.shard = t.shard, a.nshards = t.shards;
+  a.tiles_x = t.tiles_x;
+  a.n_slots = t.n_slots;
+  a.tile_map = t.balanced ? w->d_plan.get() : nullptr;
+  a.mean = d_shard_mean, a.var = d_shard_var;
+  a.tol2 = tol * tol, a.eps = eps;
+  a.stats = reinterpret_cast<unsigned long long*>(d_stats);
+  const uint64_t blocks = (t.n_slots + rpa::ERR_BLOCK - 1) / rpa::ERR_BLOCK;
+  const uint64_t grid = blocks < rpa::ERR_GRID_MAX ? blocks : rpa::ERR_GRID_MAX;
+  hipLaunchKernelGGL(rpa::error_kernel, dim3((unsigned)grid), dim3(rpa::ERR_BLOCK), 0, (hipStream_t)stream, a);
+  RP_HIP(hipGetLastError());
+  return RP_OK;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "rp_accum.h"
 #include "rp_bvh.h"
 #include "rp_denoise.h"
 #include "rp_variance.h"
@@ -1102,6 +1103,66 @@ int rph_batch_variance(uint32_t spp, uint32_t samples_per_stream, uint64_t n_pix
   if (B < 2) return fail("rph_batch_variance: needs at least two sample batches per pixel (spp > samples_per_stream)");
   for (uint64_t i = 0; i < n_pixels; i++)
     for (uint32_t c = 0; c < 3; c++) var[3 * i + c] = rpv::batch_variance(sums + 3 * i * B + c, 3, B, spp, sps);
+  return RP_OK;
+}
+
+// rp_accum.h's Welford update per word, frame after frame: what rp_accum.hip's accum_kernel does per lane.
+int rph_accum_frames(uint64_t n_words, uint32_t n_prior, uint32_t n_frames, const double* frames, uint64_t frame_stride,
+                     double* mean, double* m2, double* var) {
+  if (!frames || !mean || !m2) return fail("rph_accum_frames: frames, mean and m2 must be non-NULL");
+  if (n_words == 0) return fail("rph_accum_frames: n_words is zero");
+  if (n_frames == 0) return fail("rph_accum_frames: n_frames is zero: nothing to fold in");
+  if (frame_stride < n_words) return fail("rph_accum_frames: frame_stride is below n_words: the frames would overlap");
+  const uint64_t n = (uint64_t)n_prior + n_frames;
+  if (n > 0x7fffffffu) return fail("rph_accum_frames: more than 2^31 - 1 frames (n_prior + n_frames)");
+  if (var && n < 2) return fail("rph_accum_frames: the variance needs at least two frames (n_prior + n_frames >= 2)");
+  if (n_words > (1ull << 40) - 512) return fail("rph_accum_frames: n_words is above 2^40 - 512");
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_words;
+  auto overlaps = [](const double* a, uint64_t na, const double* b, uint64_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+  };
+  if (overlaps(mean, out_bytes, frames, in_bytes) || overlaps(m2, out_bytes, frames, in_bytes) ||
+      overlaps(var, out_bytes, frames, in_bytes))
+    return fail("rph_accum_frames: mean, m2 and var must not alias the frames");
+  if (overlaps(mean, out_bytes, m2, out_bytes) || overlaps(var, out_bytes, mean, out_bytes) ||
+      overlaps(var, out_bytes, m2, out_bytes))
+    return fail("rph_accum_frames: mean, m2 and var must not alias one another");
+  if (!n_prior)
+    for (uint64_t w = 0; w < n_words; w++) mean[w] = 0.0, m2[w] = 0.0;
+  for (uint32_t f = 0; f < n_frames; f++) {
+    const double r = rpa::frame_weight(n_prior + f + 1);
+    const double* x = frames + (uint64_t)f * frame_stride;
+    for (uint64_t w = 0; w < n_words; w++) rpa::welford(x[w], r, mean[w], m2[w]);
+  }
+  if (var) {
+    const double nn = rpa::mean_divisor((uint32_t)n);
+    for (uint64_t w = 0; w < n_words; w++) var[w] = rpa::mean_variance(m2[w], nn);
+  }
+  return RP_OK;
+}
+
+// rp_accum.h's error2 per pixel and the four order-free statistics: what rp_accum.hip's error_kernel reduces.
+int rph_accum_error(const rp_error_params* params, uint64_t n_pixels, const double* mean, const double* var,
+                    uint64_t* stats) {
+  if (!mean || !var || !stats) return fail("rph_accum_error: mean, var and stats must be non-NULL");
+  double tol, eps;
+  if (!rpa::resolve(params, tol, eps))
+    return fail("rph_accum_error: error params out of range (tol > 0; eps > 0 and finite)");
+  const double tol2 = tol * tol;
+  for (int k = 0; k < rpa::STATS_LEN; k++) stats[k] = 0;
+  for (uint64_t i = 0; i < n_pixels; i++) {
+    const double e2 = rpa::error2(mean + 3 * i, var + 3 * i, eps);
+    stats[rpa::STAT_PIXELS]++;
+    if (e2 > tol2) stats[rpa::STAT_OVER]++;
+    if (!rpa::finite(e2)) {
+      stats[rpa::STAT_NONFINITE]++;
+    } else if (e2 > 0.0) {
+      uint64_t bits;
+      std::memcpy(&bits, &e2, sizeof bits);
+      if (bits > stats[rpa::STAT_MAX_BITS]) stats[rpa::STAT_MAX_BITS] = bits;
+    }
+  }
   return RP_OK;
 }
 

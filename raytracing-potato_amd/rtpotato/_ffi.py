@@ -38,6 +38,7 @@ RP_SHARD_INTERLEAVE, RP_SHARD_BALANCED = 0, 1
 RP_STATUS_STACK_OVERFLOW, RP_STATUS_PLAN_MISMATCH = 1, 2
 RP_ABI_VERSION = 9
 RP_MAX_FRAMES = 64
+RP_ERROR_STATS_LEN = 4  # rp_accum_error_device_ws: pixels counted, pixels over, bits of the largest finite e2, non-finite
 RP_FRAME_ORDER_AUTO, RP_FRAME_ORDER_SEQUENTIAL, RP_FRAME_ORDER_INTERLEAVED, RP_FRAME_ORDER_PIXEL = 0, 1, 2, 3
 
 
@@ -114,6 +115,10 @@ class rp_denoise_var_params(Structure):  # include/rp.h: base.sigma_color is ign
     _fields_ = [("base", rp_denoise_params), ("sigma_var", c_double), ("var_eps", c_double)]
 
 
+class rp_error_params(Structure):  # include/rp.h: a zero field takes its default (tol 0.05, eps 1e-4)
+    _fields_ = [("tol", c_double), ("eps", c_double)]
+
+
 class rph_mesh(Structure):
     _fields_ = [("n_vertices", c_uint32), ("n_indices", c_uint32), ("positions", POINTER(c_double)),
                 ("normals", POINTER(c_double)), ("uvs", POINTER(c_double)), ("indices", POINTER(c_uint32))]
@@ -148,7 +153,8 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_workspace_unit_order", "rp_frames_block_words", "rp_frames_pack", "rp_frames_unpack",
               "rp_render_aov_device_ws", "rp_render_aov", "rp_denoise_params_init", "rp_denoise_scratch_bytes",
               "rp_denoise_device", "rp_denoise", "rp_render_variance_device_ws", "rp_denoise_var_params_init",
-              "rp_denoise_var_scratch_bytes", "rp_denoise_var_device", "rp_denoise_var"]
+              "rp_denoise_var_scratch_bytes", "rp_denoise_var_device", "rp_denoise_var", "rp_accum_frames_device",
+              "rp_accum_error_device_ws"]
 class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
     _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
                 ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
@@ -160,7 +166,8 @@ class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launc
 HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save", "rph_free", "rph_to_srgb_u8",
                 "rph_lookat", "rph_sky_panorama", "rph_bvh_selfcheck", "rph_bvh_traversal_stats", "rph_bvh_selfcheck_ex", "rph_bvh_traversal_stats_ex", "rph_bvh_tree_hash", "rph_last_error",
                 "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test",
-                "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance"]
+                "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
+                "rph_accum_error"]
 
 
 def rp_lib_path() -> str:
@@ -265,6 +272,10 @@ def rp() -> ctypes.CDLL:
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.rp_denoise_var.argtypes = [POINTER(rp_denoise_var_params), c_int, c_uint32, c_uint32, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double)]
+    lib.rp_accum_frames_device.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]
+    lib.rp_accum_error_device_ws.argtypes = [c_void_p, c_void_p, POINTER(rp_render_params), POINTER(rp_error_params),
+                                             c_void_p, c_void_p, c_void_p, c_void_p]
     if lib.rp_abi_version() != RP_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rp_abi_version()}, bindings expect {RP_ABI_VERSION} (rebuild)")
     _rp = lib
@@ -311,6 +322,8 @@ def host() -> ctypes.CDLL:
     lib.rph_denoise_var.argtypes = [POINTER(rp_denoise_var_params), c_uint32, c_uint32, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p]
     lib.rph_batch_variance.argtypes = [c_uint32, c_uint32, c_uint64, c_void_p, c_void_p]
+    lib.rph_accum_frames.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.rph_accum_error.argtypes = [POINTER(rp_error_params), c_uint64, c_void_p, c_void_p, c_void_p]
     _host = lib
     return lib
 

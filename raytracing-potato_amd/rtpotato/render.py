@@ -325,6 +325,101 @@ class DeviceScene:
             self.to_bgra8(replace(params, tile_w=w, tile_h=h), out, bytes_, stream=s)
             return out, bytes_
 
+    # ---- progressive rendering: running mean and variance over frames (rp_accum_*) ------
+    def accum_error_device(self, params: RenderParams, mean, var, stats, tol: float = 0.0, eps: float = 0.0,
+                           workspace: "Workspace | None" = None, stream=None) -> None:
+        """rp_accum_error_device_ws: the error statistics of the shard's pixels from `mean` and `var` (torch f64,
+        >= 3 * shard_slot_count elements, compact shard order) into `stats` (torch int64, RP_ERROR_STATS_LEN: pixels
+        counted, pixels with e2 > tol^2, the bits of the largest finite e2 -- error_stats() decodes them --, pixels whose
+        e2 is not finite) on `stream` (torch stream; default: current).  tol, eps: 0 takes the default (0.05, 1e-4).  A
+        balanced shard takes the plan of the beauty render done before on `workspace`."""
+        import torch
+        n = shard_slot_count(params)
+        for t in (mean, var):
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() >= 3 * n
+        assert stats.dtype == torch.int64 and stats.is_cuda and stats.is_contiguous()
+        assert stats.numel() >= F.RP_ERROR_STATS_LEN
+        if workspace is not None:
+            assert workspace.scene is self and workspace.handle
+        s = stream if stream is not None else torch.cuda.current_stream(mean.device)
+        p = params.to_c()
+        e = F.rp_error_params(tol, eps)
+        F.check(F.rp().rp_accum_error_device_ws(self.handle, workspace.handle if workspace else None, ctypes.byref(p),
+                                                ctypes.byref(e), mean.data_ptr(), var.data_ptr(), stats.data_ptr(),
+                                                ctypes.c_void_p(s.cuda_stream)))
+
+    def render_progressive(self, params: RenderParams, frames_per_launch: int = 4, max_frames: int = 64,
+                           tol: float = 0.05, share: float = 0.01, denoise=None, camera=None, stream=None) -> dict:
+        """Progressive rendering: launches of `frames_per_launch` frames (render_frames_device, launch number l at
+        seed + done * B * W * H with B = ceil(spp / samples_per_stream), so no stream repeats) folded on the device into
+        a running mean and the variance of that mean (accum_frames_device), until at most `share` of the pixels have a
+        relative standard error above `tol` (accum_error_device) or `max_frames` frames are in; the last launch is
+        shortened so that max_frames is met exactly.  Everything runs on `stream` (torch stream; default: current).
+        After every launch the four statistics words and the counters are read back: ONE HOST SYNCHRONISATION PER
+        LAUNCH, the price of deciding on the host whether to go on.
+        Returns {"mean", "variance": (h, w, 3) torch f64 in frame order, "frames": n, "stats": one tuple per launch
+        (frames so far, pixels, over, largest finite e2, non-finite pixels)} and, unless denoise is False, "denoised":
+        the guides of render_aov_device at spp = min(n * spp, 64), then denoise_device(variance=...) (`denoise`: as
+        denoise_var_params takes it).  One device holds the whole frame (num_shards = 1, interleave)."""
+        import torch
+        from dataclasses import replace
+        if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
+            raise ValueError("render_progressive renders the whole frame on one device (num_shards = 1, interleave)")
+        if not 1 <= frames_per_launch <= F.RP_MAX_FRAMES:
+            raise ValueError(f"frames_per_launch must be 1..{F.RP_MAX_FRAMES}, got {frames_per_launch}")
+        if min(frames_per_launch, max_frames) < 2:
+            raise ValueError("the variance needs two frames: frames_per_launch and max_frames must be >= 2")
+        if not (tol > 0.0 and 0.0 <= share <= 1.0):
+            raise ValueError(f"tol must be > 0 and share in [0, 1], got {tol}, {share}")
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        w, h, n = params.width, params.height, shard_slot_count(params)
+        nbatch = -(-params.spp // (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM))
+        self.reserve_frames(params, frames_per_launch)
+        done, log = 0, []
+        with torch.cuda.stream(s):
+            frames = torch.empty(frames_per_launch * 3 * n, dtype=torch.float64, device=dev)
+            mean, m2, var = (torch.empty(3 * n, dtype=torch.float64, device=dev) for _ in range(3))
+            ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
+            stats = torch.zeros(F.RP_ERROR_STATS_LEN, dtype=torch.int64, device=dev)
+            while done < max_frames:
+                k = min(frames_per_launch, max_frames - done)
+                q = replace(params, seed=(params.seed + done * nbatch * w * h) & 0xFFFFFFFFFFFFFFFF)
+                self.render_frames_device(q, k, frames, ctr, camera=camera, stream=s)
+                accum_frames_device(frames, k, mean, m2, n_prior=done, var=var, n_words=3 * n, stream=s)
+                self.accum_error_device(params, mean, var, stats, tol=tol, stream=s)
+                done += k
+                s.synchronize()  # the one host synchronisation of the launch: the loop's decision needs the counts
+                st, status = error_stats(stats.cpu().numpy()), int(ctr[3])
+                if status:
+                    raise RuntimeError(f"render_progressive: device status {status:#x} after {done} frames")
+                log.append((done,) + st)
+                if st[1] <= share * st[0]:
+                    break
+            p = params.to_c()
+            out = {"frames": done, "stats": log}
+            for key, t in (("mean", mean), ("variance", var)):
+                out[key] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+                F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 6, out[key].data_ptr(),
+                                                 ctypes.c_void_p(s.cuda_stream)))
+            if denoise is False:
+                return out
+            ga = replace(params, spp=min(done * params.spp, 64))
+            gp = ga.to_c()
+            guide = {}
+            shard = {k_: torch.empty(c * n, dtype=torch.float64, device=dev)
+                     for k_, c in (("normal", 3), ("albedo", 3), ("depth", 1))}
+            self.render_aov_device(ga, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
+                                   camera=camera, stream=s)
+            for k_, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
+                guide[k_] = torch.empty(t.numel() // n * w * h, dtype=torch.float64, device=dev)
+                F.check(F.rp().rp_frame_assemble(ctypes.byref(gp), t.data_ptr(), 2 * (t.numel() // n),
+                                                 guide[k_].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+            out["denoised"] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+            denoise_device(out["mean"], guide["normal"], guide["albedo"], guide["depth"], out["denoised"],
+                           params=denoise, stream=s, variance=out["variance"])
+            return out
+
     def to_bgra8(self, params: RenderParams, shard_rgb, out, stream=None) -> None:
         """Output stage on the device (rp_shard_to_bgra8): the shard's linear f64 RGB (`shard_rgb`, torch
         f64) -> to_srgb_u8 bytes in TGA order B, G, R, A into `out` (torch uint8, >= 4 * slots)."""
@@ -667,6 +762,70 @@ def batch_variance_host(sums, spp: int, samples_per_stream: int = 0) -> np.ndarr
     var = np.empty(sums.shape[:-2] + (3,), dtype=np.float64)
     F.check_host(F.host().rph_batch_variance(spp, samples_per_stream, var.size // 3, sums.ctypes.data, var.ctypes.data))
     return var
+
+
+# ---- progressive accumulation (rp_accum_*, include/rp.h) --------------------------------
+def _accum_shape(n_frames: int, n_words, stride, mean_len: int, frames_len: int):
+    n_words = mean_len if n_words is None else int(n_words)
+    stride = n_words if stride is None else int(stride)
+    # what the library would read and write must lie inside the buffers; its own refusals stay the library's
+    assert n_words <= mean_len, f"mean, m2 and var hold {mean_len} words, n_words = {n_words}"
+    if n_frames >= 1 and stride >= n_words:
+        assert frames_len >= (n_frames - 1) * stride + n_words, "frames: (n_frames - 1) * stride + n_words words"
+    return n_words, stride
+
+
+def accum_frames_device(frames, n_frames: int, mean, m2, n_prior: int = 0, var=None, n_words=None, stride=None,
+                        stream=None) -> None:
+    """rp_accum_frames_device on torch f64 tensors of one device, asynchronously on `stream` (torch stream; default:
+    current): the n_frames blocks of `frames` (block f at f * stride; stride default n_words, n_words default
+    mean.numel()) folded in order into the running `mean` and `m2`, which hold n_prior frames already (0: they are only
+    written); `var` (optional) receives the variance of the mean after n_prior + n_frames frames.  Elementwise: shard
+    buffers, full frames, anything."""
+    import torch
+    for t in (frames, mean, m2, var):
+        if t is not None:
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.device == mean.device
+    small = min(t.numel() for t in (mean, m2, var) if t is not None)
+    n_words, stride = _accum_shape(n_frames, n_words, stride, small, frames.numel())
+    s = stream if stream is not None else torch.cuda.current_stream(mean.device)
+    with torch.cuda.device(mean.device):
+        F.check(F.rp().rp_accum_frames_device(n_words, n_prior, n_frames, frames.data_ptr(), stride, mean.data_ptr(),
+                                              m2.data_ptr(), var.data_ptr() if var is not None else None,
+                                              ctypes.c_void_p(s.cuda_stream)))
+
+
+def accum_frames_host(frames, n_frames: int, mean, m2, n_prior: int = 0, var=None, n_words=None, stride=None) -> None:
+    """rph_accum_frames: the same fold on the CPU (librp_host.so; the same arithmetic header as the kernel, equal
+    bits), in place on contiguous numpy f64 arrays."""
+    for a in (frames, mean, m2, var):
+        if a is not None:
+            assert isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
+    for a in (mean, m2, var):
+        assert a is None or a.flags.writeable
+    small = min(a.size for a in (mean, m2, var) if a is not None)
+    n_words, stride = _accum_shape(n_frames, n_words, stride, small, frames.size)
+    F.check_host(F.host().rph_accum_frames(n_words, n_prior, n_frames, frames.ctypes.data, stride, mean.ctypes.data,
+                                           m2.ctypes.data, var.ctypes.data if var is not None else None))
+
+
+def error_stats(stats) -> tuple:
+    """The RP_ERROR_STATS_LEN words of an error pass as (pixels, over, largest finite e2 as a float, non-finite)."""
+    w = np.asarray(stats).reshape(-1)[:F.RP_ERROR_STATS_LEN].astype(np.uint64)
+    return int(w[0]), int(w[1]), float(w[2:3].view(np.float64)[0]), int(w[3])
+
+
+def accum_error_host(mean, var, tol: float = 0.0, eps: float = 0.0) -> np.ndarray:
+    """rph_accum_error: the error statistics of full frames mean and var ((h, w, 3) or (pixels, 3) f64) on the CPU:
+    uint64[RP_ERROR_STATS_LEN], as rp_accum_error_device_ws defines them (error_stats() decodes them)."""
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    var = np.ascontiguousarray(var, dtype=np.float64)
+    assert mean.shape == var.shape and mean.shape[-1] == 3, (mean.shape, var.shape)
+    stats = np.zeros(F.RP_ERROR_STATS_LEN, dtype=np.uint64)
+    e = F.rp_error_params(tol, eps)
+    F.check_host(F.host().rph_accum_error(ctypes.byref(e), mean.size // 3, mean.ctypes.data, var.ctypes.data,
+                                          stats.ctypes.data))
+    return stats
 
 
 def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, stream=None, variance=None) -> None:

@@ -362,6 +362,25 @@ static void check_denoise() {
   CHECK(rph_denoise_var(&v, W, H, rgb.data(), var.data(), nrm.data(), alb.data(), dep.data(), out.data()) == RP_EINVAL);
   std::printf("variance: batches of 4, 4 and 2; variance-guided denoise: misses passed through, aliasing, a missing\n"
               "variance and a negative sigma_var refused\n");
+  // progressive accumulation's host loops (csrc/rp_accum.h rph_accum_frames, rph_accum_error): the three batch frames
+  // at a stride with a gap, folded 1 + 2 with exactly sized buffers, then the error statistics of the result
+  const uint64_t nw = 3 * W * H, stride = nw + 5;
+  std::vector<double> fr(2 * stride + nw), mean(nw), m2(nw), avar(nw);
+  for (uint32_t b = 0; b < B; b++)
+    for (uint64_t i = 0; i < nw; i++) fr[b * stride + i] = sums[3 * (i / 3 * B + b) + i % 3] / (b == 2 ? 2.0 : 4.0);
+  CHECK(rph_accum_frames(nw, 0, 1, fr.data(), stride, mean.data(), m2.data(), nullptr) == RP_OK);
+  for (uint64_t i = 0; i < nw; i++) CHECK(mean[i] == fr[i] && m2[i] == 0.0);
+  CHECK(rph_accum_frames(nw, 1, 2, fr.data() + stride, stride, mean.data(), m2.data(), avar.data()) == RP_OK);
+  for (uint64_t i = 0; i < nw; i++) CHECK(avar[i] >= 0.0 && avar[i] < 1.0 && (i / 3 % 4 ? avar[i] > 0.0 : avar[i] == 0.0));
+  CHECK(rph_accum_frames(nw, 0, 1, fr.data(), stride, mean.data(), m2.data(), avar.data()) == RP_EINVAL);
+  CHECK(rph_accum_frames(nw, 0, 3, fr.data(), stride, fr.data() + nw, m2.data(), avar.data()) == RP_EINVAL);
+  uint64_t st[RP_ERROR_STATS_LEN];
+  CHECK(rph_accum_error(nullptr, W * H, mean.data(), avar.data(), st) == RP_OK);
+  CHECK(st[0] == W * H && st[1] <= st[0] && st[2] > 0 && st[3] == 0);
+  rp_error_params ep{-1.0, 0.0};
+  CHECK(rph_accum_error(&ep, W * H, mean.data(), avar.data(), st) == RP_EINVAL);
+  std::printf("accumulate: three frames at a gapped stride folded 1 + 2, error statistics; one-frame variance, aliasing\n"
+              "and a negative tolerance refused\n");
 }
 
 int main(int argc, char** argv) {
