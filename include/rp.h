@@ -615,6 +615,78 @@ int rp_accum_error_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_
                              const rp_error_params* error, const double* d_shard_mean, const double* d_shard_var,
                              uint64_t* d_stats, void* stream);
 
+/* Tile-adaptive progressive rendering: further launches trace only the tiles that are still over the
+ * tolerance.  Three calls: a render launch over a list of frame tiles, the selection of the tiles still over, and the
+ * fold of a tile-list launch into whole-frame state.  The RNG contract makes the result well defined: pixel (i, j)'s
+ * k-th frame is the frame of seed + k*W*H whoever renders it, a tile that leaves the list never returns (its state no
+ * longer changes), so every listed tile has the same number of frames folded in and one seed per launch suffices.
+ *
+ * rp_render_tiles_device_ws: n_frames frames of the n_listed frame tiles d_tiles names (device memory; row-major tile
+ * indices of `params`' frame, as everywhere else).  `params` describes the whole frame on one device: num_shards 0 or 1,
+ * shard 0, RP_SHARD_INTERLEAVE; one stream per pixel (samples_per_stream >= spp >= 1).  Frame f (0 .. n_frames - 1) is the
+ * frame of seed + f*W*H, exactly as rp_render_frames_device_ws's.  Output: listed tile k occupies the slots
+ * k*tw*th .. (k + 1)*tw*th - 1, row-major inside the tile; frame f starts at f * 3 * n_listed*tw*th doubles of d_rgb and
+ * at f * n_listed*tw*th floats of d_fg (nullable).
+ *   Defined property: every value written is bit-identical to what rp_render_frames_device_ws writes for that pixel and
+ *   frame with the same params, for every frame_order.
+ *   Not written and not counted: the slots of edge tiles outside the frame, and the slots of an entry e at or above the
+ *   frame's tile count.  The render kernel's in-frame test skips the latter by itself: slot_pixel and the unit fetch
+ *   (rp_units.h) place tile e's pixels at row (e / tiles_x) * tile_h >= tiles_y * tile_h >= height.  That holds while
+ *   e < 2^31 (the fetch's division) and e * tile_h < 2^32 (the row does not wrap); beyond that range the entry's own
+ *   slots are unspecified -- still nothing outside the entry's slots is written.  Duplicates render twice, each into its
+ *   own slots.
+ *   d_counters (RP_COUNTERS_LEN, required): zeroed on `stream`, then samples = spp x in-frame pixels of the listed tiles x
+ *   n_frames, rays and pixels likewise, status bits as rp_render_device.
+ * Asynchronous on `stream`; never allocates or synchronises.  It uses what a workspace (NULL = the scene's) has from its
+ * creation -- queues, keystream slabs, spill, start times -- and needs no reservation (the batch workspace is for
+ * several streams per pixel, which it refuses).  It leaves the workspace's learned state exactly as it found it: no tile
+ * is measured, no unit duration stored, no plan or cost table read or written; rp_workspace_frame_info reports 0 after it.
+ * It waits on a pending frame gather as a render does.  The tiles go out in list order, in the queue chunks and frame
+ * order of a shard of n_listed tiles (raytracing-potato_amd/csrc/rp_tiles_plan.h).  n_listed = 0: the counters are
+ * zeroed, nothing is launched, RP_OK.  RP_EINVAL: a NULL camera, params, d_rgb, d_counters or (n_listed > 0) d_tiles; a
+ * sharded or balanced params; spp = 0; samples_per_stream < spp; n_listed above the frame's tile count; n_frames outside
+ * 1..RP_MAX_FRAMES; a bad frame_order; what rp_render_frames_device_ws refuses about params and the launch's size. */
+int rp_render_tiles_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_camera* camera,
+                              const rp_render_params* params, const uint32_t* d_tiles, uint32_t n_listed,
+                              uint32_t n_frames, uint32_t frame_order, double* d_rgb, float* d_fg, uint64_t* d_counters,
+                              void* stream);
+
+/* rp_accum_tiles_select_device: which tiles of a list are still over.  d_mean and d_var are whole-frame compact shard
+ * buffers (one shard, interleave: frame tile t at slot t*tw*th, 3 doubles per slot) -- the layout a whole-frame render
+ * and rp_accum_frames_device keep.  d_tiles_in: n_in tile indices, NULL = the identity list 0 .. n_in - 1.  Per listed
+ * tile k:
+ *     over_k = the number of its in-frame pixels with e2 > tol*tol  (e2, tol, eps: as rp_accum_error_device_ws; NaN is
+ *              never over, +inf is)
+ *     px_k   = its in-frame pixel count
+ *     active iff (double)over_k > tile_share * (double)px_k          (tile_share in [0, 1); 0: any pixel over)
+ *   An entry at or above the frame's tile count has over = 0 and is never active.
+ * d_tiles_out (room for n_in entries) receives the active tiles in the order of the input list -- a stable compaction,
+ * the same on every run --, d_count[0] their number, d_over (nullable, n_in entries) the counts.  d_tiles_out is also the
+ * pass's scratch: entries past the count hold leftovers.  Asynchronous on `stream` on the CURRENT device, two small
+ * launches (one block per listed tile; one block for the scan), no atomics, no allocation, no synchronisation.
+ * RP_EINVAL: a NULL d_mean, d_var, d_tiles_out or d_count; sharded or balanced params; error params out of range;
+ * tile_share outside [0, 1); n_in above 16384 (the limit balanced plans have); d_tiles_out aliasing d_tiles_in or d_over,
+ * d_count inside either output. */
+int rp_accum_tiles_select_device(const rp_render_params* params, const rp_error_params* error, double tile_share,
+                                 const double* d_mean, const double* d_var, const uint32_t* d_tiles_in, uint32_t n_in,
+                                 uint32_t* d_over, uint32_t* d_tiles_out, uint32_t* d_count, void* stream);
+
+/* rp_accum_frames_tiles_device: rp_accum_frames_device's fold with a block indirection, as ignorant of scenes.  The
+ * state (d_mean, d_m2, d_var nullable) is n_state_tiles blocks of tile_words doubles; d_frames holds n_frames frames of
+ * n_listed blocks, word w of listed block k of frame f at d_frames[f*frame_stride + k*tile_words + w].  Listed block k
+ * is folded in frame order, with frame numbers n_prior + 1 .., into the state words d_tiles[k]*tile_words + w; d_var is
+ * written for the listed blocks only, with n = n_prior + n_frames.  The arithmetic is the definition above, unchanged;
+ * every other state word is untouched (with n_prior = 0 the listed blocks' state is not read, the others' is kept).
+ * An entry at or above n_state_tiles is skipped.  Duplicate entries give an unspecified result for that block and for
+ * nothing else.  tile_words even, 16-byte aligned buffers and an even stride take the wide path, anything else the
+ * 8-byte one.  Asynchronous on `stream` on the CURRENT device; one launch (none for n_listed = 0, which is RP_OK).
+ * RP_EINVAL: as rp_accum_frames_device (tile_words for n_words; the state's n_state_tiles*tile_words above 2^40 - 512),
+ * and n_listed > n_state_tiles, frame_stride < n_listed*tile_words, a NULL d_tiles with n_listed > 0, an output aliasing
+ * the list. */
+int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, const uint32_t* d_tiles, uint32_t n_listed,
+                                 uint32_t n_prior, uint32_t n_frames, const double* d_frames, uint64_t frame_stride,
+                                 double* d_mean, double* d_m2, double* d_var, void* stream);
+
 /* Output stage on the device: the reference's to_srgb_u8 (utility.rs:212-220, alpha 255) of every slot of
  * a compact shard buffer, bytes in tga::save's pixel order B, G, R, A (image.rs:116-137), so a gathered
  * and de-interleaved frame is the body of the reference's output.tga (18-byte header: rph_tga_save).

@@ -185,6 +185,35 @@ int rph_accum_frames(uint64_t n_words, uint32_t n_prior, uint32_t n_frames, cons
 int rph_accum_error(const rp_error_params* params, uint64_t n_pixels, const double* mean, const double* var,
                     uint64_t* stats);
 
+/* Tile-adaptive progressive rendering on the CPU (include/rp.h rp_accum_frames_tiles_device and
+ * rp_accum_tiles_select_device: the definitions): plain loops over raytracing-potato_amd/csrc/rp_accum.h, the header the
+ * device kernels compile, so values agree bit for bit and counts, list and order exactly.  Host buffers, the device
+ * calls' arguments and RP_EINVAL cases; rph_accum_tiles_select also serves tiles_out == tiles_in (compaction in place). */
+int rph_accum_frames_tiles(uint64_t tile_words, uint32_t n_state_tiles, const uint32_t* tiles, uint32_t n_listed,
+                           uint32_t n_prior, uint32_t n_frames, const double* frames, uint64_t frame_stride, double* mean,
+                           double* m2, double* var);
+int rph_accum_tiles_select(const rp_render_params* params, const rp_error_params* error, double tile_share,
+                           const double* mean, const double* var, const uint32_t* tiles_in, uint32_t n_in, uint32_t* over,
+                           uint32_t* tiles_out, uint32_t* count);
+
+/* Test hooks: what rp_render_tiles_device_ws launches with (raytracing-potato_amd/csrc/rp_tiles_plan.h
+ * rps::plan_tiles_launch, the header librp.so's rp_tiles.hip calls), in the pattern of rph_plan_launch and rph_unit_walk
+ * for a whole-frame params given field by field (shard 0 of 1, interleave).  rph_plan_tiles_launch fills the
+ * rph_launch_plan of a launch over n_listed tiles (n_shard_tiles = n_listed; plan_block 1, gather_stride and block_words
+ * 0: no gather), and returns the launch's own refusal.  rph_tiles_unit_walk runs rp_units.h's fetch on the CPU with the
+ * list `tiles` (n_listed entries) as the launch's tile map: units, units_cap, n_units, queue_words and entries as
+ * rph_unit_walk's.  An entry at or above the frame's tile count must simply yield no unit; one at or above 2^31 ends the
+ * walk with RP_EINVAL (the fetch's division). */
+int rph_plan_tiles_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w,
+                          uint32_t tile_h, uint32_t samples_per_stream, uint32_t n_listed, uint32_t n_frames,
+                          uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes,
+                          rph_launch_plan* out);
+int rph_tiles_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w,
+                        uint32_t tile_h, uint32_t samples_per_stream, uint32_t n_frames, uint32_t frame_order,
+                        uint32_t unit_queues, uint32_t queue_chunk, const uint32_t* tiles, uint32_t n_listed,
+                        uint32_t n_blocks, uint32_t* units, uint64_t units_cap, uint64_t* n_units, uint32_t* queue_words,
+                        uint32_t* entries);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

@@ -52,6 +52,20 @@ RPA_FN bool resolve(const P* in, double& tol, double& eps) {
   return tol > 0.0 && eps > 0.0 && finite(eps);
 }
 
+// Tile selection (include/rp.h rp_accum_tiles_select_device).  A pixel is over when e2 > tol^2: a NaN
+// compares false and is never over, +inf is.  Frame tile t of a W x H frame in tw x th tiles, tiles_x per row, holds
+// tile_pixels in-frame pixels (t below the frame's tile count), and stays active when more than tile_share of them are
+// over -- both sides as doubles, so over == tile_share * px exactly is not active.
+RPA_FN bool pixel_over(const double* m, const double* v, double eps, double tol2) { return error2(m, v, eps) > tol2; }
+RPA_FN uint32_t tile_pixels(uint32_t t, uint32_t W, uint32_t H, uint32_t tw, uint32_t th, uint32_t tiles_x) {
+  const uint32_t ox = (t % tiles_x) * tw, oy = (t / tiles_x) * th;
+  const uint32_t nx = W - ox < tw ? W - ox : tw, ny = H - oy < th ? H - oy : th;
+  return nx * ny;
+}
+RPA_FN bool tile_active(uint32_t over, uint32_t px, double tile_share) {
+  return (double)over > tile_share * (double)px;
+}
+
 // The four statistics of an error pass (RP_ERROR_STATS_LEN): all order-free -- integer sums and an integer maximum of
 // the bit patterns of positive doubles, which order as the doubles do.
 enum { STAT_PIXELS = 0, STAT_OVER = 1, STAT_MAX_BITS = 2, STAT_NONFINITE = 3, STATS_LEN = 4 };

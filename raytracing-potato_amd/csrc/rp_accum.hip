@@ -11,6 +11,9 @@
 // loads and stores when every pointer is 16-byte aligned and the frame stride is even; otherwise, and for an odd last
 // word, it walks its words one by one.  The loads of ACC_GROUP frames are issued before the Welford chain that consumes
 // them in frame order; 1 / k is one division per frame, the same in every lane.  The grid is ceil(n_words / 2) lanes.
+// accum_tiles_kernel (rp_accum_frames_tiles_device): the same per-lane body with a block indirection --
+// the words of listed block k of every frame folded into state block tiles[k], an entry at or above the state's block
+// count skipped; the wide path needs an even block size as well, so that every block starts on an even word.
 // error_kernel: a lane per shard slot, several slots per lane above 2048 blocks (rp_units.h slot_pixel's decode, as
 // rp_variance.hip); the four statistics are
 // reduced in the wave, then in the block through LDS, then one vector atomic per block and statistic -- integer sums and
@@ -61,9 +64,10 @@ __device__ __forceinline__ void store(double* p, const Words<2>& w) {
   *reinterpret_cast<double2*>(p) = make_double2(w.v[0], w.v[1]);
 }
 
-// Words w .. w + W - 1 through every frame of the call, in frame order.
+// Words ws .. ws + W - 1 of every frame of the call, in frame order, into the state words w .. w + W - 1 (the plain
+// fold: ws = w; the tile fold: ws inside listed block k, w inside state block tiles[k]).
 template <int W>
-__device__ __forceinline__ void fold(const AccArgs& A, uint64_t w) {
+__device__ __forceinline__ void fold(const AccArgs& A, uint64_t ws, uint64_t w) {
   Words<W> mean, m2;
   if (A.n_prior) {
     mean = load<W>(A.mean + w);
@@ -72,7 +76,7 @@ __device__ __forceinline__ void fold(const AccArgs& A, uint64_t w) {
 #pragma unroll
     for (int c = 0; c < W; c++) mean.v[c] = 0.0, m2.v[c] = 0.0;
   }
-  const double* src = A.frames + w;
+  const double* src = A.frames + ws;
   uint32_t k = A.n_prior;  // frames folded in so far
   uint32_t f = 0;
   for (; f + ACC_GROUP <= A.n_frames; f += ACC_GROUP) {
@@ -107,10 +111,35 @@ __global__ void __launch_bounds__(ACC_BLOCK) accum_kernel(const AccArgs A) {
   const uint64_t w = 2 * ((uint64_t)blockIdx.x * ACC_BLOCK + threadIdx.x);
   if (w >= A.n_words) return;
   if (A.vec && w + 1 < A.n_words) {
-    fold<2>(A, w);
+    fold<2>(A, w, w);
   } else {
-    fold<1>(A, w);
-    if (w + 1 < A.n_words) fold<1>(A, w + 1);
+    fold<1>(A, w, w);
+    if (w + 1 < A.n_words) fold<1>(A, w + 1, w + 1);
+  }
+}
+
+// The tile fold (rp_accum_frames_tiles_device): A.n_words is a block's words here.  A lane owns two consecutive words
+// of one listed block; an entry at or above n_state would address words past the state and is skipped.
+struct TileArgs {
+  AccArgs A;
+  const uint32_t* tiles;
+  uint32_t n_listed, n_state;
+  uint64_t lanes_per_tile;  // ceil(A.n_words / 2)
+};
+
+__global__ void __launch_bounds__(ACC_BLOCK) accum_tiles_kernel(const TileArgs T) {
+  const uint64_t id = (uint64_t)blockIdx.x * ACC_BLOCK + threadIdx.x;
+  const uint64_t k = id / T.lanes_per_tile;
+  if (k >= T.n_listed) return;
+  const uint32_t t = T.tiles[k];
+  if (t >= T.n_state) return;
+  const uint64_t w = 2 * (id - k * T.lanes_per_tile), tw = T.A.n_words;
+  const uint64_t src = k * tw + w, dst = (uint64_t)t * tw + w;
+  if (T.A.vec && w + 1 < tw) {  // (vec: tw is even, so src and dst are)
+    fold<2>(T.A, src, dst);
+  } else {
+    fold<1>(T.A, src, dst);
+    if (w + 1 < tw) fold<1>(T.A, src + 1, dst + 1);
   }
 }
 
@@ -222,6 +251,46 @@ int rp_accum_frames_device(uint64_t n_words, uint32_t n_prior, uint32_t n_frames
   a.vec = bits % 16 == 0 && frame_stride % 2 == 0;
   a.frames = d_frames, a.mean = d_mean, a.m2 = d_m2, a.var = d_var;
   hipLaunchKernelGGL(rpa::accum_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, a);
+  RP_HIP(hipGetLastError());
+  return RP_OK;
+}
+
+int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, const uint32_t* d_tiles, uint32_t n_listed,
+                                 uint32_t n_prior, uint32_t n_frames, const double* d_frames, uint64_t frame_stride,
+                                 double* d_mean, double* d_m2, double* d_var, void* stream) {
+  if (!d_frames || !d_mean || !d_m2) return fail(RP_EINVAL, "d_frames, d_mean and d_m2 must be non-NULL");
+  if (tile_words == 0) return fail(RP_EINVAL, "tile_words is zero");
+  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
+  if (n_listed > n_state_tiles) return fail(RP_EINVAL, "n_listed is above n_state_tiles");
+  if (n_listed && !d_tiles) return fail(RP_EINVAL, "d_tiles must be non-NULL");
+  if (tile_words > (1ull << 40) - 512 || (uint64_t)n_state_tiles * tile_words > (1ull << 40) - 512)
+    return fail(RP_EINVAL, "the state is above 2^40 - 512 words (n_state_tiles * tile_words)");
+  const uint64_t n_words = (uint64_t)n_listed * tile_words, n_state = (uint64_t)n_state_tiles * tile_words;
+  if (frame_stride < n_words) return fail(RP_EINVAL, "frame_stride is below n_listed * tile_words: the frames would overlap");
+  const uint64_t n = (uint64_t)n_prior + n_frames;
+  if (n > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames (n_prior + n_frames)");
+  if (d_var && n < 2) return fail(RP_EINVAL, "the variance needs at least two frames (n_prior + n_frames >= 2)");
+  if (n_listed == 0) return RP_OK;  // nothing listed: nothing folded, nothing launched
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_state;
+  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
+    if (rpa::overlaps(o, out_bytes, d_frames, in_bytes) || rpa::overlaps(o, out_bytes, d_tiles, 4ull * n_listed))
+      return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias the frames or the list");
+  if (rpa::overlaps(d_mean, out_bytes, d_m2, out_bytes) || rpa::overlaps(d_var, out_bytes, d_mean, out_bytes) ||
+      rpa::overlaps(d_var, out_bytes, d_m2, out_bytes))
+    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
+  rpa::TileArgs t;
+  t.A.n_words = tile_words, t.A.stride = frame_stride;
+  t.A.n_prior = n_prior, t.A.n_frames = n_frames;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(d_frames) | reinterpret_cast<uintptr_t>(d_mean) |
+                         reinterpret_cast<uintptr_t>(d_m2) | reinterpret_cast<uintptr_t>(d_var);
+  // the wide path: every block starts on an even word of 16-byte aligned buffers, in the frames and in the state
+  t.A.vec = bits % 16 == 0 && frame_stride % 2 == 0 && tile_words % 2 == 0;
+  t.A.frames = d_frames, t.A.mean = d_mean, t.A.m2 = d_m2, t.A.var = d_var;
+  t.tiles = d_tiles, t.n_listed = n_listed, t.n_state = n_state_tiles;
+  t.lanes_per_tile = (tile_words + 1) / 2;
+  const uint64_t lanes = t.lanes_per_tile * n_listed, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
+  if (grid > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 blocks");
+  hipLaunchKernelGGL(rpa::accum_tiles_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, t);
   RP_HIP(hipGetLastError());
   return RP_OK;
 }

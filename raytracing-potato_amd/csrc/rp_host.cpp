@@ -21,6 +21,7 @@
 #include "rp_kernel.h"
 #include "rp_ray.h"
 #include "rp_schedule.h"
+#include "rp_tiles_plan.h"
 #include "rp_units.h"
 
 namespace {
@@ -1163,6 +1164,176 @@ int rph_accum_error(const rp_error_params* params, uint64_t n_pixels, const doub
       if (bits > stats[rpa::STAT_MAX_BITS]) stats[rpa::STAT_MAX_BITS] = bits;
     }
   }
+  return RP_OK;
+}
+
+// rp_accum_frames_tiles_device on host buffers: rph_accum_frames' loop per listed block, an entry at or above
+// n_state_tiles skipped (what rp_accum.hip's accum_tiles_kernel does per lane).
+int rph_accum_frames_tiles(uint64_t tile_words, uint32_t n_state_tiles, const uint32_t* tiles, uint32_t n_listed,
+                           uint32_t n_prior, uint32_t n_frames, const double* frames, uint64_t frame_stride, double* mean,
+                           double* m2, double* var) {
+  if (!frames || !mean || !m2) return fail("rph_accum_frames_tiles: frames, mean and m2 must be non-NULL");
+  if (tile_words == 0) return fail("rph_accum_frames_tiles: tile_words is zero");
+  if (n_frames == 0) return fail("rph_accum_frames_tiles: n_frames is zero: nothing to fold in");
+  if (n_listed > n_state_tiles) return fail("rph_accum_frames_tiles: n_listed is above n_state_tiles");
+  if (n_listed && !tiles) return fail("rph_accum_frames_tiles: tiles must be non-NULL");
+  if (tile_words > (1ull << 40) - 512 || (uint64_t)n_state_tiles * tile_words > (1ull << 40) - 512)
+    return fail("rph_accum_frames_tiles: the state is above 2^40 - 512 words (n_state_tiles * tile_words)");
+  const uint64_t n_words = (uint64_t)n_listed * tile_words, n_state = (uint64_t)n_state_tiles * tile_words;
+  if (frame_stride < n_words)
+    return fail("rph_accum_frames_tiles: frame_stride is below n_listed * tile_words: the frames would overlap");
+  const uint64_t n = (uint64_t)n_prior + n_frames;
+  if (n > 0x7fffffffu) return fail("rph_accum_frames_tiles: more than 2^31 - 1 frames (n_prior + n_frames)");
+  if (var && n < 2) return fail("rph_accum_frames_tiles: the variance needs at least two frames (n_prior + n_frames >= 2)");
+  if (n_listed == 0) return RP_OK;
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_state;
+  auto overlaps = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+  };
+  for (const double* o : {(const double*)mean, (const double*)m2, (const double*)var})
+    if (overlaps(o, out_bytes, frames, in_bytes) || overlaps(o, out_bytes, tiles, 4ull * n_listed))
+      return fail("rph_accum_frames_tiles: mean, m2 and var must not alias the frames or the list");
+  if (overlaps(mean, out_bytes, m2, out_bytes) || overlaps(var, out_bytes, mean, out_bytes) ||
+      overlaps(var, out_bytes, m2, out_bytes))
+    return fail("rph_accum_frames_tiles: mean, m2 and var must not alias one another");
+  const double nn = var ? rpa::mean_divisor((uint32_t)n) : 0.0;
+  for (uint32_t k = 0; k < n_listed; k++) {
+    if (tiles[k] >= n_state_tiles) continue;
+    double* mk = mean + (uint64_t)tiles[k] * tile_words;
+    double* qk = m2 + (uint64_t)tiles[k] * tile_words;
+    if (!n_prior)
+      for (uint64_t w = 0; w < tile_words; w++) mk[w] = 0.0, qk[w] = 0.0;
+    for (uint32_t f = 0; f < n_frames; f++) {
+      const double r = rpa::frame_weight(n_prior + f + 1);
+      const double* x = frames + (uint64_t)f * frame_stride + (uint64_t)k * tile_words;
+      for (uint64_t w = 0; w < tile_words; w++) rpa::welford(x[w], r, mk[w], qk[w]);
+    }
+    if (var) {
+      double* vk = var + (uint64_t)tiles[k] * tile_words;
+      for (uint64_t w = 0; w < tile_words; w++) vk[w] = rpa::mean_variance(qk[w], nn);
+    }
+  }
+  return RP_OK;
+}
+
+// rp_accum_tiles_select_device on host buffers: rp_accum.h's pixel_over per in-frame pixel of every listed tile, the
+// tile's count, tile_active, and the active tiles in list order (what rp_tiles.hip's two kernels do).
+int rph_accum_tiles_select(const rp_render_params* params, const rp_error_params* error, double tile_share,
+                           const double* mean, const double* var, const uint32_t* tiles_in, uint32_t n_in, uint32_t* over,
+                           uint32_t* tiles_out, uint32_t* count) {
+  if (!mean || !var || !tiles_out || !count)
+    return fail("rph_accum_tiles_select: mean, var, tiles_out and count must be non-NULL");
+  rps::Tiling t;
+  const rps::Refusal r = rps::make_tiling(params, t);
+  if (r.code) return fail(std::string("rph_accum_tiles_select: ") + r.msg);
+  if (t.shards != 1 || params->shard_map != RP_SHARD_INTERLEAVE)
+    return fail("rph_accum_tiles_select: the state is a whole frame's: num_shards 0 or 1, shard 0, interleave");
+  double tol, eps;
+  if (!rpa::resolve(error, tol, eps))
+    return fail("rph_accum_tiles_select: error params out of range (tol > 0; eps > 0 and finite)");
+  if (!(tile_share >= 0.0 && tile_share < 1.0)) return fail("rph_accum_tiles_select: tile_share must be in [0, 1)");
+  if (n_in > (uint32_t)rpk::TILE_SORT_MAX) return fail("rph_accum_tiles_select: n_in is above 16384 (rpk::TILE_SORT_MAX)");
+  const double tol2 = tol * tol;
+  const uint32_t W = params->width, H = params->height, tile_px = t.tw * t.th;
+  uint32_t n_out = 0;
+  for (uint32_t k = 0; k < n_in; k++) {
+    const uint32_t tile = tiles_in ? tiles_in[k] : k;
+    uint32_t n_over = 0;
+    const bool in_frame = tile < t.n_tiles;
+    if (in_frame) {
+      const uint32_t ox = (tile % t.tiles_x) * t.tw, oy = (tile / t.tiles_x) * t.th;
+      for (uint32_t lj = 0; lj < t.th && oy + lj < H; lj++)
+        for (uint32_t li = 0; li < t.tw && ox + li < W; li++) {
+          const uint64_t slot = (uint64_t)tile * tile_px + (uint64_t)lj * t.tw + li;
+          n_over += rpa::pixel_over(mean + 3 * slot, var + 3 * slot, eps, tol2);
+        }
+    }
+    if (over) over[k] = n_over;
+    // (tiles_out may be tiles_in here: position n_out is never beyond entry k, which has been read)
+    if (in_frame && rpa::tile_active(n_over, rpa::tile_pixels(tile, W, H, t.tw, t.th, t.tiles_x), tile_share))
+      tiles_out[n_out++] = tile;
+  }
+  count[0] = n_out;
+  return RP_OK;
+}
+
+// The plan of a tile-list launch (rp_tiles_plan.h rps::plan_tiles_launch, what rp_render_tiles_device_ws launches with).
+static rps::Refusal tiles_plan(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w,
+                               uint32_t tile_h, uint32_t samples_per_stream, uint32_t n_listed, uint32_t n_frames,
+                               uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes,
+                               rps::LaunchPlan& lp, bool& planned) {
+  const rp_render_params p = scalar_params(width, height, spp, max_bounce, tile_w, tile_h, 0, 1, samples_per_stream,
+                                           RP_SHARD_INTERLEAVE);
+  rp_scene_options opt{};
+  opt.unit_queues = unit_queues;
+  opt.queue_chunk = queue_chunk;
+  planned = false;
+  rps::Refusal r = rps::plan_tiles_launch(&p, n_listed, n_frames, frame_order, opt, lp);
+  if (r.code) return r;
+  planned = true;
+  return rps::launch_limits(lp, lanes);
+}
+
+int rph_plan_tiles_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w,
+                          uint32_t tile_h, uint32_t samples_per_stream, uint32_t n_listed, uint32_t n_frames,
+                          uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes,
+                          rph_launch_plan* out) {
+  if (!out) return fail("rph_plan_tiles_launch: out is NULL");
+  *out = rph_launch_plan{};
+  rps::LaunchPlan lp{};
+  bool planned;
+  const rps::Refusal r = tiles_plan(width, height, spp, max_bounce, tile_w, tile_h, samples_per_stream, n_listed, n_frames,
+                                    frame_order, unit_queues, queue_chunk, lanes, lp, planned);
+  if (planned) {
+    const rpk::KParams& kp = lp.kp;
+    out->n_shard_tiles = lp.t.n_shard_tiles;
+    out->nbatch = lp.t.nbatch;
+    out->plan_block = 1;
+    out->n_slots = lp.t.n_slots;
+    out->queue_groups = kp.queue_groups;
+    out->queue_chunk = kp.queue_chunk;
+    out->frames_inter = kp.frames_inter;
+    out->sortable = lp.sortable;
+    out->measure = lp.measure;
+    out->grid = (uint32_t)rps::grid_for(kp.n_queue, lanes / rpk::RENDER_BLOCK);
+    out->n_queue = kp.n_queue;
+    out->out_stride = kp.out_stride;
+    const rpk::Div32 dv[3] = {kp.dv_units, kp.dv_tiles_x, kp.dv_chunk};
+    uint32_t* const dst[3] = {out->dv_units, out->dv_tiles_x, out->dv_chunk};
+    for (int i = 0; i < 3; i++) dst[i][0] = dv[i].m, dst[i][1] = dv[i].s;
+  }
+  if (r.code) {
+    g_err = r.msg;
+    return r.code;
+  }
+  return RP_OK;
+}
+
+int rph_tiles_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w,
+                        uint32_t tile_h, uint32_t samples_per_stream, uint32_t n_frames, uint32_t frame_order,
+                        uint32_t unit_queues, uint32_t queue_chunk, const uint32_t* tiles, uint32_t n_listed,
+                        uint32_t n_blocks, uint32_t* units, uint64_t units_cap, uint64_t* n_units, uint32_t* queue_words,
+                        uint32_t* entries) {
+  if (!n_units || !queue_words || !entries || (units_cap && !units) || n_blocks == 0 || (n_listed && !tiles))
+    return fail("rph_tiles_unit_walk: NULL list or output, or no blocks");
+  rps::LaunchPlan lp{};
+  bool planned;
+  const rps::Refusal r = tiles_plan(width, height, spp, max_bounce, tile_w, tile_h, samples_per_stream, n_listed, n_frames,
+                                    frame_order, unit_queues, queue_chunk, n_blocks, lp, planned);
+  if (r.code) {
+    g_err = r.msg;
+    return r.code;
+  }
+  UnitWalk W;
+  W.a.P = lp.kp;
+  W.a.P.tile_map = tiles;  // rp_tiles.hip: the list is the one-shard launch's tile map
+  W.a.queue = W.words;
+  *n_units = n_listed ? walk_units<false>(W, n_blocks, units, units_cap) : 0;
+  std::memcpy(queue_words, W.words, sizeof W.words);
+  std::memcpy(entries, W.entries, sizeof W.entries);
+  if (W.err) return fail(W.err);
+  if (*n_units > units_cap) return fail("rph_tiles_unit_walk: more units than units_cap");
   return RP_OK;
 }
 

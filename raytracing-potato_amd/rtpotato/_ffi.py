@@ -154,7 +154,8 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_render_aov_device_ws", "rp_render_aov", "rp_denoise_params_init", "rp_denoise_scratch_bytes",
               "rp_denoise_device", "rp_denoise", "rp_render_variance_device_ws", "rp_denoise_var_params_init",
               "rp_denoise_var_scratch_bytes", "rp_denoise_var_device", "rp_denoise_var", "rp_accum_frames_device",
-              "rp_accum_error_device_ws"]
+              "rp_accum_error_device_ws", "rp_render_tiles_device_ws", "rp_accum_tiles_select_device",
+              "rp_accum_frames_tiles_device"]
 class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
     _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
                 ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
@@ -167,7 +168,8 @@ HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save",
                 "rph_lookat", "rph_sky_panorama", "rph_bvh_selfcheck", "rph_bvh_traversal_stats", "rph_bvh_selfcheck_ex", "rph_bvh_traversal_stats_ex", "rph_bvh_tree_hash", "rph_last_error",
                 "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
-                "rph_accum_error"]
+                "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
+                "rph_tiles_unit_walk"]
 
 
 def rp_lib_path() -> str:
@@ -276,6 +278,12 @@ def rp() -> ctypes.CDLL:
                                            c_void_p]
     lib.rp_accum_error_device_ws.argtypes = [c_void_p, c_void_p, POINTER(rp_render_params), POINTER(rp_error_params),
                                              c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.rp_render_tiles_device_ws.argtypes = [c_void_p, c_void_p, POINTER(rp_camera), POINTER(rp_render_params), c_void_p,
+                                              c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.rp_accum_tiles_select_device.argtypes = [POINTER(rp_render_params), POINTER(rp_error_params), c_double, c_void_p,
+                                                 c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.rp_accum_frames_tiles_device.argtypes = [c_uint64, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p,
+                                                 c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]
     if lib.rp_abi_version() != RP_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rp_abi_version()}, bindings expect {RP_ABI_VERSION} (rebuild)")
     _rp = lib
@@ -324,6 +332,13 @@ def host() -> ctypes.CDLL:
     lib.rph_batch_variance.argtypes = [c_uint32, c_uint32, c_uint64, c_void_p, c_void_p]
     lib.rph_accum_frames.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]
     lib.rph_accum_error.argtypes = [POINTER(rp_error_params), c_uint64, c_void_p, c_void_p, c_void_p]
+    lib.rph_accum_frames_tiles.argtypes = [c_uint64, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint64,
+                                           c_void_p, c_void_p, c_void_p]
+    lib.rph_accum_tiles_select.argtypes = [POINTER(rp_render_params), POINTER(rp_error_params), c_double, c_void_p,
+                                           c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p]
+    lib.rph_plan_tiles_launch.argtypes = [c_uint32] * 12 + [c_uint64, POINTER(rph_launch_plan)]
+    lib.rph_tiles_unit_walk.argtypes = [c_uint32] * 11 + [c_void_p, c_uint32, c_uint32, c_void_p, c_uint64,
+                                        POINTER(c_uint64), c_void_p, c_void_p]
     _host = lib
     return lib
 

@@ -396,29 +396,150 @@ class DeviceScene:
                 log.append((done,) + st)
                 if st[1] <= share * st[0]:
                     break
-            p = params.to_c()
-            out = {"frames": done, "stats": log}
-            for key, t in (("mean", mean), ("variance", var)):
-                out[key] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
-                F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 6, out[key].data_ptr(),
-                                                 ctypes.c_void_p(s.cuda_stream)))
-            if denoise is False:
-                return out
-            ga = replace(params, spp=min(done * params.spp, 64))
-            gp = ga.to_c()
-            guide = {}
-            shard = {k_: torch.empty(c * n, dtype=torch.float64, device=dev)
-                     for k_, c in (("normal", 3), ("albedo", 3), ("depth", 1))}
-            self.render_aov_device(ga, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
-                                   camera=camera, stream=s)
-            for k_, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
-                guide[k_] = torch.empty(t.numel() // n * w * h, dtype=torch.float64, device=dev)
-                F.check(F.rp().rp_frame_assemble(ctypes.byref(gp), t.data_ptr(), 2 * (t.numel() // n),
-                                                 guide[k_].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
-            out["denoised"] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
-            denoise_device(out["mean"], guide["normal"], guide["albedo"], guide["depth"], out["denoised"],
-                           params=denoise, stream=s, variance=out["variance"])
+            return self._progressive_result(params, mean, var, done, {"frames": done, "stats": log}, denoise, camera, s)
+
+    def _progressive_result(self, params: RenderParams, mean, var, frames: int, out: dict, denoise, camera, s) -> dict:
+        """What render_progressive and render_adaptive return from their state (compact shard buffers, on stream s,
+        which is current): "mean" and "variance" in frame order (rp_frame_assemble) and, unless denoise is False,
+        "denoised" with the guides at min(frames * spp, 64) spp."""
+        import torch
+        from dataclasses import replace
+        dev = mean.device
+        w, h, n = params.width, params.height, shard_slot_count(params)
+        p = params.to_c()
+        for key, t in (("mean", mean), ("variance", var)):
+            out[key] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+            F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 6, out[key].data_ptr(),
+                                             ctypes.c_void_p(s.cuda_stream)))
+        if denoise is False:
             return out
+        ga = replace(params, spp=min(frames * params.spp, 64))
+        gp = ga.to_c()
+        guide = {}
+        shard = {k_: torch.empty(c * n, dtype=torch.float64, device=dev)
+                 for k_, c in (("normal", 3), ("albedo", 3), ("depth", 1))}
+        self.render_aov_device(ga, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
+                               camera=camera, stream=s)
+        for k_, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
+            guide[k_] = torch.empty(t.numel() // n * w * h, dtype=torch.float64, device=dev)
+            F.check(F.rp().rp_frame_assemble(ctypes.byref(gp), t.data_ptr(), 2 * (t.numel() // n),
+                                             guide[k_].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+        out["denoised"] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
+        denoise_device(out["mean"], guide["normal"], guide["albedo"], guide["depth"], out["denoised"],
+                       params=denoise, stream=s, variance=out["variance"])
+        return out
+
+    # ---- tile-adaptive progressive rendering (rp_render_tiles_device_ws, rp_accum_tiles_*; DESIGN.md 4.14) ------
+    def render_tiles_device(self, params: RenderParams, tiles, n_listed: int, n_frames: int, out, counters, fg=None,
+                            camera=None, stream=None, workspace: "Workspace | None" = None, order="auto") -> None:
+        """rp_render_tiles_device_ws: n_frames frames of the n_listed frame tiles `tiles` names (torch int32 on the
+        scene's device, row-major tile indices of the whole frame `params` describes), frame f at seed + f * W * H.
+        out: torch f64, listed tile k at slot k * tw * th, frame f at f * 3 * n_listed * tw * th; fg likewise in floats or
+        None; counters: int64, RP_COUNTERS_LEN, zeroed and filled by the launch.  One stream per pixel only."""
+        import torch
+        cam = (camera or self.scene.camera).to_c()
+        p = params.to_c()
+        slots = n_listed * (params.tile_w or 32) * (params.tile_h or 32)
+        assert tiles is None or (tiles.dtype == torch.int32 and tiles.is_cuda and tiles.is_contiguous()
+                                 and tiles.numel() >= n_listed)
+        assert out.dtype == torch.float64 and out.is_cuda and out.numel() >= 3 * slots * n_frames
+        assert fg is None or (fg.dtype == torch.float32 and fg.numel() >= slots * n_frames)
+        assert counters.dtype == torch.int64 and counters.is_cuda and counters.numel() >= F.RP_COUNTERS_LEN
+        if workspace is not None:
+            assert workspace.scene is self and workspace.handle
+        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        F.check(F.rp().rp_render_tiles_device_ws(
+            self.handle, workspace.handle if workspace else None, ctypes.byref(cam), ctypes.byref(p),
+            tiles.data_ptr() if tiles is not None else None, n_listed, n_frames,
+            {"auto": F.RP_FRAME_ORDER_AUTO, "sequential": F.RP_FRAME_ORDER_SEQUENTIAL,
+             "interleaved": F.RP_FRAME_ORDER_INTERLEAVED, "pixel": F.RP_FRAME_ORDER_PIXEL}.get(order, order),
+            out.data_ptr(), fg.data_ptr() if fg is not None else None, counters.data_ptr(),
+            ctypes.c_void_p(s.cuda_stream)))
+
+    def render_adaptive(self, params: RenderParams, frames_per_launch: int = 4, max_frames: int = 64,
+                        max_launch_frames: int = 16, tol: float = 0.05, share: float = 0.01, tile_share=None,
+                        denoise=None, camera=None, stream=None) -> dict:
+        """Tile-adaptive progressive rendering: render_progressive's first launch over the whole frame, then launches
+        over the tiles still over the tolerance only.  After every launch accum_tiles_select_device keeps, of the current
+        list, the tiles with more than `tile_share` (default: share) of their pixels over `tol`; the loop stops when the
+        list is empty, when at most `share` of all pixels are over, or at max_frames.  With A of T tiles active a launch
+        renders k = min(max_launch_frames, max_frames - done, frames_per_launch * (T // A)) frames of them
+        (render_tiles_device at seed + done * W * H) and folds them with accum_frames_tiles_device: about the first
+        launch's unit count, always inside its frames buffer.  ONE HOST SYNCHRONISATION PER LAUNCH, as
+        render_progressive.  One stream per pixel (samples_per_stream >= spp), one device, at most 16384 tiles.
+        Returns {"mean", "variance": (h, w, 3) torch f64 in frame order -- each pixel the progressive mean of its own
+        tile's first n_t frames, and the variance of that mean --, "tile_frames": (tiles_y, tiles_x) int32 numpy, n_t,
+        "frames": the largest n_t, "samples", "rays": the counters' sums, "log": per launch (frames done before it, its
+        tiles, its frames) + error_stats after it, "launch_ms": per launch the device time of its render, fold, error
+        pass and select (events on the stream)} and, unless denoise is False, "denoised" as render_progressive's."""
+        import torch
+        from dataclasses import replace
+        if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
+            raise ValueError("render_adaptive renders the whole frame on one device (num_shards = 1, interleave)")
+        if not 1 <= frames_per_launch <= F.RP_MAX_FRAMES:
+            raise ValueError(f"frames_per_launch must be 1..{F.RP_MAX_FRAMES}, got {frames_per_launch}")
+        if not 1 <= max_launch_frames <= F.RP_MAX_FRAMES:
+            raise ValueError(f"max_launch_frames must be 1..{F.RP_MAX_FRAMES}, got {max_launch_frames}")
+        if min(frames_per_launch, max_frames) < 2:
+            raise ValueError("the variance needs two frames: frames_per_launch and max_frames must be >= 2")
+        if not (tol > 0.0 and 0.0 <= share <= 1.0):
+            raise ValueError(f"tol must be > 0 and share in [0, 1], got {tol}, {share}")
+        tile_share = share if tile_share is None else tile_share
+        if not 0.0 <= tile_share < 1.0:
+            raise ValueError(f"tile_share must be in [0, 1), got {tile_share}")
+        if params.spp < 1 or (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM) < params.spp:
+            raise ValueError("render_adaptive needs one stream per pixel: 1 <= spp <= samples_per_stream")
+        dev = torch.device("cuda", self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        w, h, n = params.width, params.height, shard_slot_count(params)
+        tw, th = params.tile_w or 32, params.tile_h or 32
+        tiles_x, tiles_y = -(-w // tw), -(-h // th)
+        T, tile_words = tiles_x * tiles_y, 3 * tw * th
+        if T > 16384:
+            raise ValueError(f"render_adaptive selects among at most 16384 tiles, the frame has {T}")
+        self.reserve_frames(params, frames_per_launch)
+        tile_frames = np.zeros(T, dtype=np.int32)
+        done, log, samples, rays = 0, [], 0, 0
+        with torch.cuda.stream(s):
+            frames = torch.empty(frames_per_launch * 3 * n, dtype=torch.float64, device=dev)
+            mean, m2, var = (torch.empty(3 * n, dtype=torch.float64, device=dev) for _ in range(3))
+            ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
+            stats = torch.zeros(F.RP_ERROR_STATS_LEN, dtype=torch.int64, device=dev)
+            lists = [torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2)]
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+            cur, active, listed = None, T, np.arange(T)  # the list the next select reads: None = identity
+            k = min(frames_per_launch, max_frames)
+            marks = [torch.cuda.Event(enable_timing=True)]  # one before the first launch, one after every select
+            marks[0].record(s)
+            self.render_frames_device(params, k, frames, ctr, camera=camera, stream=s)
+            accum_frames_device(frames, k, mean, m2, n_prior=0, var=var, n_words=3 * n, stream=s)
+            while True:
+                self.accum_error_device(params, mean, var, stats, tol=tol, stream=s)
+                nxt = lists[1] if cur is lists[0] else lists[0]
+                accum_tiles_select_device(params, mean, var, nxt, count, tiles_in=cur, n_in=active, tol=tol,
+                                          tile_share=tile_share, stream=s)
+                marks.append(torch.cuda.Event(enable_timing=True))
+                marks[-1].record(s)
+                s.synchronize()  # the one host synchronisation of the launch: the loop's decision needs the counts
+                c = ctr.cpu().numpy()
+                st, n_next = error_stats(stats.cpu().numpy()), int(count[0])
+                if int(c[3]):
+                    raise RuntimeError(f"render_adaptive: device status {int(c[3]):#x} after {done + k} frames")
+                rays, samples = rays + int(c[0]), samples + int(c[1])
+                tile_frames[listed] += k
+                log.append((done, active, k) + st)
+                done += k
+                if n_next == 0 or st[1] <= share * st[0] or done == max_frames:
+                    break
+                cur, active, listed = nxt, n_next, nxt[:n_next].cpu().numpy()
+                k = min(max_launch_frames, max_frames - done, frames_per_launch * (T // active))
+                q = replace(params, seed=(params.seed + done * w * h) & 0xFFFFFFFFFFFFFFFF)
+                self.render_tiles_device(q, cur, active, k, frames, ctr, camera=camera, stream=s)
+                accum_frames_tiles_device(frames, k, cur, active, tile_words, mean, m2, n_prior=done, var=var,
+                                          n_state_tiles=T, stream=s)
+            out = {"frames": done, "tile_frames": tile_frames.reshape(tiles_y, tiles_x), "samples": samples,
+                   "rays": rays, "log": log, "launch_ms": [a.elapsed_time(b) for a, b in zip(marks, marks[1:])]}
+            return self._progressive_result(params, mean, var, done, out, denoise, camera, s)
 
     def to_bgra8(self, params: RenderParams, shard_rgb, out, stream=None) -> None:
         """Output stage on the device (rp_shard_to_bgra8): the shard's linear f64 RGB (`shard_rgb`, torch
@@ -826,6 +947,110 @@ def accum_error_host(mean, var, tol: float = 0.0, eps: float = 0.0) -> np.ndarra
     F.check_host(F.host().rph_accum_error(ctypes.byref(e), mean.size // 3, mean.ctypes.data, var.ctypes.data,
                                           stats.ctypes.data))
     return stats
+
+
+# ---- tile-adaptive progressive rendering (rp_accum_tiles_*, include/rp.h) ----------------
+def accum_tiles_select_device(params: RenderParams, mean, var, tiles_out, count, tiles_in=None, n_in=None, over=None,
+                              tol: float = 0.0, eps: float = 0.0, tile_share: float = 0.0, stream=None) -> None:
+    """rp_accum_tiles_select_device on torch tensors of one device, asynchronously on `stream` (torch stream; default:
+    current): of the n_in tiles `tiles_in` lists (int32; None = the identity list 0 .. n_in - 1, n_in default: the
+    list's length or the frame's tile count), those with more than tile_share of their in-frame pixels over the
+    tolerance go, in list order, to `tiles_out` (int32, >= n_in) and their number to count[0] (int32); `over` (int32,
+    >= n_in, optional) receives every listed tile's count.  mean, var: the whole frame's compact shard buffers (f64)."""
+    import torch
+    n = shard_slot_count(params)
+    for t in (mean, var):
+        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() >= 3 * n
+    if n_in is None:
+        n_in = tiles_in.numel() if tiles_in is not None else n // ((params.tile_w or 32) * (params.tile_h or 32))
+    for t, m in ((tiles_in, n_in), (over, n_in), (tiles_out, n_in), (count, 1)):
+        assert t is None or (t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= m
+                             and t.device == mean.device)
+    s = stream if stream is not None else torch.cuda.current_stream(mean.device)
+    p = params.to_c()
+    e = F.rp_error_params(tol, eps)
+    with torch.cuda.device(mean.device):
+        F.check(F.rp().rp_accum_tiles_select_device(
+            ctypes.byref(p), ctypes.byref(e), tile_share, mean.data_ptr(), var.data_ptr(),
+            tiles_in.data_ptr() if tiles_in is not None else None, n_in, over.data_ptr() if over is not None else None,
+            tiles_out.data_ptr(), count.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+
+
+def accum_tiles_select_host(params: RenderParams, mean, var, tiles_in=None, n_in=None, tol: float = 0.0,
+                            eps: float = 0.0, tile_share: float = 0.0) -> tuple:
+    """rph_accum_tiles_select: the same selection on the CPU (librp_host.so; the same arithmetic header as the kernels).
+    mean, var: contiguous numpy f64, the whole frame's compact shard buffers.  Returns (active tiles in list order,
+    every listed tile's over count), both uint32."""
+    for a in (mean, var):
+        assert isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
+        assert a.size >= 3 * shard_slot_count(params)
+    if tiles_in is not None:
+        tiles_in = np.ascontiguousarray(tiles_in, dtype=np.uint32)
+    if n_in is None:
+        n_in = tiles_in.size if tiles_in is not None else (
+            shard_slot_count(params) // ((params.tile_w or 32) * (params.tile_h or 32)))
+    assert tiles_in is None or tiles_in.size >= n_in
+    over = np.zeros(max(n_in, 1), dtype=np.uint32)
+    out = np.zeros(max(n_in, 1), dtype=np.uint32)
+    count = np.zeros(1, dtype=np.uint32)
+    p = params.to_c()
+    e = F.rp_error_params(tol, eps)
+    F.check_host(F.host().rph_accum_tiles_select(
+        ctypes.byref(p), ctypes.byref(e), tile_share, mean.ctypes.data, var.ctypes.data,
+        tiles_in.ctypes.data if tiles_in is not None else None, n_in, over.ctypes.data, out.ctypes.data,
+        count.ctypes.data))
+    return out[:int(count[0])].copy(), over[:n_in].copy()
+
+
+def _tiles_shape(n_frames: int, n_listed: int, tile_words: int, stride, n_state_tiles, state_len: int, frames_len: int):
+    stride = n_listed * tile_words if stride is None else int(stride)
+    n_state_tiles = state_len // tile_words if n_state_tiles is None and tile_words > 0 else int(n_state_tiles or 0)
+    # what the library would read and write must lie inside the buffers; its own refusals stay the library's
+    assert n_state_tiles * tile_words <= state_len, f"mean, m2 and var hold {state_len} words"
+    if n_frames >= 1 and stride >= n_listed * tile_words:
+        assert frames_len >= (n_frames - 1) * stride + n_listed * tile_words, "frames: too short for the listed blocks"
+    return stride, n_state_tiles
+
+
+def accum_frames_tiles_device(frames, n_frames: int, tiles, n_listed: int, tile_words: int, mean, m2, n_prior: int = 0,
+                              var=None, stride=None, n_state_tiles=None, stream=None) -> None:
+    """rp_accum_frames_tiles_device on torch tensors of one device, asynchronously on `stream` (torch stream; default:
+    current): listed block k (tile_words doubles at f * stride + k * tile_words of `frames`; stride default n_listed *
+    tile_words) of the n_frames frames folded in order into block tiles[k] (int32) of the running `mean` and `m2`
+    (n_state_tiles blocks, default what they hold), which hold n_prior frames already; `var` (optional) is written for
+    the listed blocks.  Every other block is untouched; an entry >= n_state_tiles is skipped."""
+    import torch
+    for t in (frames, mean, m2, var):
+        if t is not None:
+            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.device == mean.device
+    assert tiles is None or (tiles.dtype == torch.int32 and tiles.is_cuda and tiles.is_contiguous()
+                             and tiles.numel() >= n_listed and tiles.device == mean.device)
+    small = min(t.numel() for t in (mean, m2, var) if t is not None)
+    stride, n_state_tiles = _tiles_shape(n_frames, n_listed, tile_words, stride, n_state_tiles, small, frames.numel())
+    s = stream if stream is not None else torch.cuda.current_stream(mean.device)
+    with torch.cuda.device(mean.device):
+        F.check(F.rp().rp_accum_frames_tiles_device(
+            tile_words, n_state_tiles, tiles.data_ptr() if tiles is not None else None, n_listed, n_prior, n_frames,
+            frames.data_ptr(), stride, mean.data_ptr(), m2.data_ptr(), var.data_ptr() if var is not None else None,
+            ctypes.c_void_p(s.cuda_stream)))
+
+
+def accum_frames_tiles_host(frames, n_frames: int, tiles, n_listed: int, tile_words: int, mean, m2, n_prior: int = 0,
+                            var=None, stride=None, n_state_tiles=None) -> None:
+    """rph_accum_frames_tiles: the same fold on the CPU (librp_host.so; equal bits), in place on contiguous numpy f64
+    arrays; tiles: uint32 (or anything np.ascontiguousarray converts)."""
+    for a in (frames, mean, m2, var):
+        if a is not None:
+            assert isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
+    for a in (mean, m2, var):
+        assert a is None or a.flags.writeable
+    tiles = np.ascontiguousarray(tiles if tiles is not None else [], dtype=np.uint32)
+    assert tiles.size >= n_listed
+    small = min(a.size for a in (mean, m2, var) if a is not None)
+    stride, n_state_tiles = _tiles_shape(n_frames, n_listed, tile_words, stride, n_state_tiles, small, frames.size)
+    F.check_host(F.host().rph_accum_frames_tiles(
+        tile_words, n_state_tiles, tiles.ctypes.data if tiles.size else None, n_listed, n_prior, n_frames,
+        frames.ctypes.data, stride, mean.ctypes.data, m2.ctypes.data, var.ctypes.data if var is not None else None))
 
 
 def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, stream=None, variance=None) -> None:

@@ -383,11 +383,73 @@ static void check_denoise() {
               "and a negative tolerance refused\n");
 }
 
+// tile-adaptive progressive rendering's host code (csrc/rp_accum.h and csrc/rp_tiles_plan.h: rph_accum_frames_tiles,
+// rph_accum_tiles_select, rph_plan_tiles_launch, rph_tiles_unit_walk) on a 37 x 21 frame in 8 x 4 tiles (5 x 6 tiles,
+// both edges ragged), every buffer exactly sized: the fold and the select over a shuffled list with an entry outside
+// the frame, the compaction in place, the plan over every list length and the fetch over the foreign list
+static void check_tiles() {
+  const uint32_t W = 37, H = 21, tw = 8, th = 4, n_tiles = 30, tile_px = tw * th, tile_words = 3 * tile_px;
+  std::vector<uint32_t> list = {29, 3, 30, 17, 0, 4, 24};  // 30: not a tile of the frame
+  const uint32_t n_listed = (uint32_t)list.size(), frames = 3;
+  const uint64_t state = (uint64_t)n_tiles * tile_words, stride = (uint64_t)n_listed * tile_words;
+  std::vector<double> fr(frames * stride), mean(state, 0.5), m2(state, 0.0), var(state, 0.0);
+  for (uint64_t i = 0; i < fr.size(); i++) fr[i] = 0.25 + 0.001 * (double)((i * 2654435761ull) % 997);
+  CHECK(rph_accum_frames_tiles(tile_words, n_tiles, list.data(), n_listed, 0, frames, fr.data(), stride, mean.data(),
+                               m2.data(), var.data()) == RP_OK);
+  CHECK(mean[(uint64_t)29 * tile_words] != 0.5 && mean[(uint64_t)1 * tile_words] == 0.5 && var[0] > 0.0);
+  CHECK(rph_accum_frames_tiles(tile_words, n_tiles, list.data(), n_listed, 3, 1, fr.data(), stride, mean.data(), m2.data(),
+                               nullptr) == RP_OK);
+  CHECK(rph_accum_frames_tiles(tile_words, 6, list.data(), n_listed, 0, frames, fr.data(), stride, mean.data(), m2.data(),
+                               var.data()) == RP_EINVAL);
+  CHECK(rph_accum_frames_tiles(tile_words, n_tiles, list.data(), n_listed, 0, frames, fr.data(), stride - 1, mean.data(),
+                               m2.data(), var.data()) == RP_EINVAL);
+  rp_render_params p{};
+  p.width = W, p.height = H, p.spp = 4, p.max_bounce = 8, p.tile_w = tw, p.tile_h = th, p.samples_per_stream = 4;
+  std::vector<uint32_t> over(n_listed), out(n_listed);
+  uint32_t count = 99;
+  CHECK(rph_accum_tiles_select(&p, nullptr, 0.0, mean.data(), var.data(), list.data(), n_listed, over.data(), out.data(),
+                               &count) == RP_OK);
+  CHECK(count <= n_listed - 1 && over[2] == 0);
+  for (uint32_t i = 0; i < count; i++) CHECK(out[i] < n_tiles);
+  std::vector<uint32_t> all(n_tiles);
+  CHECK(rph_accum_tiles_select(&p, nullptr, 0.5, mean.data(), var.data(), nullptr, n_tiles, nullptr, all.data(), &count) == RP_OK);
+  CHECK(rph_accum_tiles_select(&p, nullptr, 0.0, mean.data(), var.data(), list.data(), n_listed, nullptr, list.data(),
+                               &count) == RP_OK);  // in place
+  CHECK(rph_accum_tiles_select(&p, nullptr, 1.0, mean.data(), var.data(), nullptr, n_tiles, nullptr, all.data(), &count) == RP_EINVAL);
+  CHECK(rph_accum_tiles_select(&p, nullptr, 0.0, mean.data(), var.data(), nullptr, 16385, nullptr, all.data(), &count) == RP_EINVAL);
+  list = {29, 3, 30, 17, 0, 4, 24};
+  rph_launch_plan o;
+  for (uint32_t n = 0; n <= n_tiles + 1; n++)
+    for (uint32_t q = 0; q < 4; q++) {
+      const int rc = rph_plan_tiles_launch(W, H, 4, 8, tw, th, 4, n, 1 + 5 * q, q, q, q * 3, 262144, &o);
+      CHECK(rc == (n <= n_tiles ? RP_OK : RP_EINVAL));
+      if (rc == RP_OK) CHECK(o.queue_chunk >= 1 && o.grid >= 1 && o.n_slots == (uint64_t)n * tile_px);
+    }
+  CHECK(rph_plan_tiles_launch(W, H, 4, 8, tw, th, 2, 3, 1, 0, 0, 0, 262144, &o) == RP_EINVAL);
+  std::vector<uint32_t> units((size_t)RPH_UNIT_WORDS * n_listed * tile_px * frames), words(RPH_QUEUE_WORDS),
+      entries(RPH_QUEUE_WORDS);
+  uint64_t n = 0, want = 0;
+  for (uint32_t t : list)
+    if (t < n_tiles) want += (uint64_t)std::min(tw, W - (t % 5) * tw) * std::min(th, H - (t / 5) * th);
+  for (uint32_t order : {RP_FRAME_ORDER_SEQUENTIAL, RP_FRAME_ORDER_INTERLEAVED, RP_FRAME_ORDER_PIXEL}) {
+    CHECK(rph_tiles_unit_walk(W, H, 4, 8, tw, th, 4, frames, order, RP_QUEUES_XCD_TILES, 3, list.data(), n_listed, 11,
+                              units.data(), units.size() / RPH_UNIT_WORDS, &n, words.data(), entries.data()) == RP_OK);
+    CHECK(n == want * frames);
+    for (uint64_t u = 0; u < n; u++)
+      CHECK(units[RPH_UNIT_WORDS * u] < n_listed * tile_px && units[RPH_UNIT_WORDS * u + 1] < W && units[RPH_UNIT_WORDS * u + 2] < H);
+  }
+  CHECK(rph_tiles_unit_walk(W, H, 4, 8, tw, th, 4, frames, 0, 0, 0, list.data(), n_listed, 11, units.data(), 10, &n,
+                            words.data(), entries.data()) == RP_EINVAL);
+  std::printf("tiles: a shuffled list with an entry outside the frame folded, selected (in place too), planned and walked;\n"
+              "a short state, a short stride, a full tile share, 16385 entries and a short unit buffer refused\n");
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
   check_plan();
   check_unit_walk();
   check_denoise();
+  check_tiles();
   MeshScene a = soup(200000, 11);  // >= 2^16 primitives: the parallel build form (rp_bvh.cpp ParallelBuild) runs
   check_tree("soup", a.desc);
   MeshScene b = grid_with_degenerates(40, 3);
