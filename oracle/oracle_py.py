@@ -17,6 +17,23 @@ LIB_FAST = os.path.join(HERE, "liboracle_fast.so")  # timed CPU baseline (-O3, n
 N_COUNTERS = 7  # rays, box tests, triangle tests, sphere tests, samples, triangle hits, texel fetches
 COUNTER_NAMES = ["rays", "box_tests", "tri_tests", "sphere_tests", "samples", "tri_hits", "texels"]
 
+# The shading census (rp_oracle.h OR_E_*): which branch of the shading each path vertex took.  Reported by
+# OracleScene.render_events only; event k of EVENT_NAMES is counter N_COUNTERS + k and bit k of the pixel mask.
+EVENT_NAMES = [
+    "hit_tri", "hit_sph", "hit_miss", "hit_tri_mesh1",
+    "sc_none", "sc_lambert", "sc_lambert_back", "sc_metal", "sc_metal_back", "sc_metal_below",
+    "sc_diel_inside", "sc_diel_reflect", "sc_diel_refract", "sc_diel_tir", "depth_out",
+    "ab_black_body", "ab_white_body", "ab_albedo", "ab_albedo_map",
+    "em_none", "em_debug_normals", "em_color", "em_sky_gradient", "em_sky_sphere",
+    "ems_debug_normals", "ems_color", "ems_sky_gradient", "ems_sky_sphere",
+    "bg_none", "bg_debug_normals", "bg_color", "bg_sky_gradient", "bg_sky_sphere",
+    "tx_missing", "tx_debug_uvs", "tx_solid", "tx_image", "tx_noise", "tx_perlin",
+    "tx_checker_even", "tx_checker_odd", "tx_checker_in_checker", "tx_image_in_checker",
+    "tx_clamp_x_lo", "tx_clamp_x_hi", "tx_clamp_y_lo", "tx_clamp_y_hi",
+    "tx_on_tri", "tx_on_sph", "tx_on_miss", "hit_two_tex", "hit_two_img",
+]
+assert len(EVENT_NAMES) <= 64
+
 _libs = {}
 
 
@@ -70,6 +87,7 @@ def lib(fast: bool = False) -> ctypes.CDLL:
     L.or_scene_info.argtypes = [vp, vp, vp]
     L.or_intersect.argtypes = [vp, vp, u64, vp, vp, vp]
     L.or_render.argtypes = [vp, vp, vp, vp, vp, vp, i32]
+    L.or_render_events.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
     L.or_render_baseline.argtypes = [vp, vp, u32, u32, u32, u32, u32, u32, u64, vp, vp]
     L.or_render_baseline.restype = dbl
     L.or_obj_load.argtypes = [ctypes.c_char_p, vp]
@@ -186,6 +204,18 @@ class OracleScene:
         if rc != 0:
             raise ValueError("or_render failed")
         return rgb, fg, dict(zip(COUNTER_NAMES, ctr.tolist()))
+
+    def render_events(self, camera_addr: int, params_addr: int, width: int, height: int, threads: int = 8):
+        """render() with the shading census: (rgb, counters by name -- COUNTER_NAMES then EVENT_NAMES --, mask),
+        mask (height, width) uint64 with bit k set where the pixel's samples produced event EVENT_NAMES[k]."""
+        rgb = np.zeros((height, width, 3))
+        ctr = np.zeros(N_COUNTERS + len(EVENT_NAMES), dtype=np.uint64)
+        mask = np.zeros((height, width), dtype=np.uint64)
+        rc = self._lib.or_render_events(self.h, camera_addr, params_addr, rgb.ctypes.data, None, ctr.ctypes.data,
+                                        mask.ctypes.data, threads)
+        if rc != 0:
+            raise ValueError("or_render_events failed")
+        return rgb, dict(zip(COUNTER_NAMES + EVENT_NAMES, ctr.tolist())), mask
 
     def baseline(self, camera_addr: int, width: int, height: int, spp: int, max_bounce: int = 8, tile: int = 32,
                  workers: int = 4, seed: int = 0, want_image: bool = False):

@@ -25,8 +25,10 @@
  * counted (the Mrays/s numerator). */
 #ifdef OR_NO_EVENT_COUNTERS
 #define OR_EVENT(C, k) ((void)0)
+#define OR_CENSUS(stmt) ((void)0)
 #else
 #define OR_EVENT(C, k) ((C)->c[k]++)
+#define OR_CENSUS(stmt) do { stmt; } while (0)  /* bookkeeping of the shading census (rp_oracle.h OR_E_*) */
 #endif
 
 /* ================================================================ RNG ======================== */
@@ -342,7 +344,14 @@ struct or_scene {
   node_t* nodes;
 };
 
-typedef struct { uint64_t c[OR_C_N]; } ctr_t;
+typedef struct {
+  uint64_t c[OR_C_N];
+#ifndef OR_NO_EVENT_COUNTERS
+  /* census context of the hit being shaded: OR_E_TX_ON_* of its kind, textures / Images evaluated for it so
+   * far, and how many Checkers the current tex_sample is nested in */
+  uint32_t where, ntex, nimg, in_checker;
+#endif
+} ctr_t;
 
 /* mesh.rs:25-30 get_triangle (positions only for bounding boxes) */
 static inline v3 vpos(const mesh_t* m, uint32_t vi) { return V(m->pos[3 * vi], m->pos[3 * vi + 1], m->pos[3 * vi + 2]); }
@@ -519,7 +528,12 @@ int or_scene_info(const or_scene* s, uint32_t* n_nodes, uint32_t* depth) {
 
 /* ---- intersection ---- */
 
-typedef struct { int valid; hit_t h; uint32_t material; } hitm_t;
+typedef struct {
+  int valid; hit_t h; uint32_t material;
+#ifndef OR_NO_EVENT_COUNTERS
+  uint32_t ekind, emesh;  /* census: OR_E_HIT_TRI / OR_E_HIT_SPH and the triangle's mesh index */
+#endif
+} hitm_t;
 
 /* hittable.rs:39-63 */
 static hitm_t hit_sphere(const rp_hittable* sp, const ray_t* r, ctr_t* C) {
@@ -546,6 +560,7 @@ static hitm_t hit_sphere(const rp_hittable* sp, const ray_t* r, ctr_t* C) {
   res.h.u = 0.5 - atan2(res.h.n.z, res.h.n.x) / TAU_;
   res.h.v = asin(res.h.n.y) / PI_ + 0.5;
   res.material = sp->material;
+  OR_CENSUS(res.ekind = OR_E_HIT_SPH; res.emesh = 0);
   return res;
 }
 
@@ -581,6 +596,7 @@ static hitm_t hit_triangle(const or_scene* s, const rp_hittable* tr, const ray_t
   res.h.u = (w * m->uv[2 * i0] + u * m->uv[2 * i1]) + v * m->uv[2 * i2];
   res.h.v = (w * m->uv[2 * i0 + 1] + u * m->uv[2 * i1 + 1]) + v * m->uv[2 * i2 + 1];
   res.material = m->material;
+  OR_CENSUS(res.ekind = OR_E_HIT_TRI; res.emesh = tr->mesh);
   return res;
 }
 
@@ -647,7 +663,7 @@ int or_intersect(or_scene* s, const double* rays, uint64_t n, double* out_hit, u
       out_material[i] = 0xffffffffu;
     }
   }
-  if (counters) for (int k = 0; k < OR_C_N; k++) counters[k] += C.c[k];
+  if (counters) for (int k = 0; k < OR_C_N_BASE; k++) counters[k] += C.c[k];
   return 0;
 }
 
@@ -666,17 +682,19 @@ static inline double mix(double a, double b, double t) { return (b - a) * t + a;
 static v3 tex_sample(const or_scene* s, uint32_t tid, const hit_t* h, ctr_t* C) {
   const tex_t* t = &s->tex[tid];
   switch (t->kind) {
-    case RP_TEXTURE_MISSING: return V(0.0, 0.0, 0.0);
-    case RP_TEXTURE_DEBUG_UVS: return V(h->u, h->v, 0.0);
-    case RP_TEXTURE_SOLID: return V(t->color[0], t->color[1], t->color[2]);
+    case RP_TEXTURE_MISSING: OR_EVENT(C, OR_E_TX_MISSING); return V(0.0, 0.0, 0.0);
+    case RP_TEXTURE_DEBUG_UVS: OR_EVENT(C, OR_E_TX_DEBUG_UVS); return V(h->u, h->v, 0.0);
+    case RP_TEXTURE_SOLID: OR_EVENT(C, OR_E_TX_SOLID); return V(t->color[0], t->color[1], t->color[2]);
     case RP_TEXTURE_IMAGE: {  /* texture.rs:40-49 */
       double w = (double)t->w, hh = (double)t->h;
       double x = h->u * w, y = h->v * hh;
+      OR_EVENT(C, OR_E_TX_IMAGE);
+      OR_CENSUS(C->nimg++; if (C->in_checker) C->c[OR_E_TX_IMAGE_IN_CHECKER]++);
       /* f64::clamp: NaN passes through, then `as u32` saturates (NaN -> 0) */
-      if (x < 0.0) x = 0.0;
-      if (x > w - 1.0) x = w - 1.0;
-      if (y < 0.0) y = 0.0;
-      if (y > hh - 1.0) y = hh - 1.0;
+      if (x < 0.0) { x = 0.0; OR_EVENT(C, OR_E_TX_CLAMP_X_LO); }
+      if (x > w - 1.0) { x = w - 1.0; OR_EVENT(C, OR_E_TX_CLAMP_X_HI); }
+      if (y < 0.0) { y = 0.0; OR_EVENT(C, OR_E_TX_CLAMP_Y_LO); }
+      if (y > hh - 1.0) { y = hh - 1.0; OR_EVENT(C, OR_E_TX_CLAMP_Y_HI); }
       uint32_t i = sat_u32(x), j = sat_u32(y);
       const uint8_t* px = t->rgba + 4 * ((size_t)i + (size_t)j * t->w);
       OR_EVENT(C, OR_C_TEXELS);
@@ -684,17 +702,23 @@ static v3 tex_sample(const or_scene* s, uint32_t tid, const hit_t* h, ctr_t* C) 
     }
     case RP_TEXTURE_CHECKER: {  /* texture.rs:51-60 */
       v3 p = h->p;
-      if (fmod(floor(p.x) + floor(p.y) + floor(p.z), 2.0) == 0.0) return tex_sample(s, t->even, h, C);
-      return tex_sample(s, t->odd, h, C);
+      int even = fmod(floor(p.x) + floor(p.y) + floor(p.z), 2.0) == 0.0;
+      OR_EVENT(C, even ? OR_E_TX_CHECKER_EVEN : OR_E_TX_CHECKER_ODD);
+      OR_CENSUS(if (C->in_checker) C->c[OR_E_TX_CHECKER_IN_CHECKER]++; C->in_checker++);
+      v3 r = tex_sample(s, even ? t->even : t->odd, h, C);
+      OR_CENSUS(C->in_checker--);
+      return r;
     }
     case RP_TEXTURE_NOISE: {  /* texture.rs:62-68 */
       v3 p = h->p;
+      OR_EVENT(C, OR_E_TX_NOISE);
       double x = or_noise_real(sat_i64(floor(p.x)), sat_i64(floor(p.y)), sat_i64(floor(p.z)), t->seed);
       x = 0.5 * x + 0.5;
       return V(x, x, x);
     }
     case RP_TEXTURE_PERLIN: {  /* texture.rs:83-118 */
       v3 p = h->p;
+      OR_EVENT(C, OR_E_TX_PERLIN);
       v3 fp = V(floor(p.x), floor(p.y), floor(p.z));
       int64_t flx = sat_i64(fp.x), fly = sat_i64(fp.y), flz = sat_i64(fp.z);
       int64_t clx = (int64_t)((uint64_t)flx + 1), cly = (int64_t)((uint64_t)fly + 1), clz = (int64_t)((uint64_t)flz + 1);
@@ -728,7 +752,9 @@ static v3 emit_eval(const or_scene* s, const rp_emit* e, const ray_t* in, const 
       double t = 0.5 * (in->d.y / sqrt(norm2(in->d)) + 1.0);
       return add(smul(1.0 - t, V(1.0, 1.0, 1.0)), smul(t, V(0.5, 0.7, 1.0)));
     }
-    case RP_EMIT_SKY_SPHERE: return tex_sample(s, e->texture, h, C);
+    case RP_EMIT_SKY_SPHERE:
+      OR_CENSUS(C->ntex++; C->c[C->where]++);
+      return tex_sample(s, e->texture, h, C);
   }
   return V(0.0, 0.0, 0.0);
 }
@@ -736,36 +762,42 @@ static v3 emit_eval(const or_scene* s, const rp_emit* e, const ray_t* in, const 
 /* material.rs:74-81 Absorb::evaluate */
 static v3 absorb_eval(const or_scene* s, const rp_absorb* a, const hit_t* h, ctr_t* C) {
   switch (a->kind) {
-    case RP_ABSORB_BLACK_BODY: return V(0.0, 0.0, 0.0);
-    case RP_ABSORB_WHITE_BODY: return V(1.0, 1.0, 1.0);
-    case RP_ABSORB_ALBEDO: return V(a->color[0], a->color[1], a->color[2]);
-    case RP_ABSORB_ALBEDO_MAP: return tex_sample(s, a->texture, h, C);
+    case RP_ABSORB_BLACK_BODY: OR_EVENT(C, OR_E_AB_BLACK_BODY); return V(0.0, 0.0, 0.0);
+    case RP_ABSORB_WHITE_BODY: OR_EVENT(C, OR_E_AB_WHITE_BODY); return V(1.0, 1.0, 1.0);
+    case RP_ABSORB_ALBEDO: OR_EVENT(C, OR_E_AB_ALBEDO); return V(a->color[0], a->color[1], a->color[2]);
+    case RP_ABSORB_ALBEDO_MAP:
+      OR_EVENT(C, OR_E_AB_ALBEDO_MAP);
+      OR_CENSUS(C->ntex++; C->c[C->where]++);
+      return tex_sample(s, a->texture, h, C);
   }
   return V(0.0, 0.0, 0.0);
 }
 
 /* material.rs:27-34 + 115-179 Scatter::evaluate; returns 1 and fills *out when a ray is scattered */
-static int scatter_eval(const rp_scatter* sc, const ray_t* in, const hit_t* h, or_rng* rng, ray_t* out) {
+static int scatter_eval(const rp_scatter* sc, const ray_t* in, const hit_t* h, or_rng* rng, ray_t* out, ctr_t* C) {
+  (void)C;
   out->o = h->p; out->tmin = RAY_EPSILON; out->tmax = INFINITY;
   switch (sc->kind) {
-    case RP_SCATTER_NONE: return 0;
+    case RP_SCATTER_NONE: OR_EVENT(C, OR_E_SC_NONE); return 0;
     case RP_SCATTER_LAMBERT: {  /* material.rs:115-130 */
-      if (dot(h->n, in->d) > 0.0) return 0;
+      if (dot(h->n, in->d) > 0.0) { OR_EVENT(C, OR_E_SC_LAMBERT_BACK); return 0; }
       double us[3]; or_sample_unit_sphere(rng, us);
       out->d = normalize(add(h->n, V(us[0], us[1], us[2])));
+      OR_EVENT(C, OR_E_SC_LAMBERT);
       return 1;
     }
     case RP_SCATTER_METAL: {  /* material.rs:132-152 */
-      if (dot(h->n, in->d) > 0.0) return 0;
+      if (dot(h->n, in->d) > 0.0) { OR_EVENT(C, OR_E_SC_METAL_BACK); return 0; }
       double ub[3]; or_sample_unit_ball(rng, ub);
       v3 rd = normalize(add(reflect(in->d, h->n), smul(sc->param, V(ub[0], ub[1], ub[2]))));
-      if (dot(h->n, rd) < 0.0) return 0;
+      if (dot(h->n, rd) < 0.0) { OR_EVENT(C, OR_E_SC_METAL_BELOW); return 0; }
       out->d = rd;
+      OR_EVENT(C, OR_E_SC_METAL);
       return 1;
     }
     case RP_SCATTER_DIELECTRIC: {  /* material.rs:154-179 */
       double eta; v3 n;
-      if (dot(h->n, in->d) > 0.0) { eta = sc->param; n = neg(h->n); }
+      if (dot(h->n, in->d) > 0.0) { eta = sc->param; n = neg(h->n); OR_EVENT(C, OR_E_SC_DIEL_INSIDE); }
       else { eta = 1.0 / sc->param; n = h->n; }
       double r0 = (1.0 - eta) / (1.0 + eta);
       r0 = r0 * r0;                                  /* powi(2) */
@@ -774,8 +806,9 @@ static int scatter_eval(const rp_scatter* sc, const ray_t* in, const hit_t* h, o
       double x5 = x * (x2 * x2);                     /* powi(5): LLVM binary expansion */
       double reflectance = r0 + (1.0 - r0) * x5;
       v3 dir;
-      if (or_sample_bernoulli(rng, reflectance)) dir = reflect(in->d, n);
-      else if (!refract(in->d, n, eta, &dir)) dir = reflect(in->d, n);
+      if (or_sample_bernoulli(rng, reflectance)) { dir = reflect(in->d, n); OR_EVENT(C, OR_E_SC_DIEL_REFLECT); }
+      else if (!refract(in->d, n, eta, &dir)) { dir = reflect(in->d, n); OR_EVENT(C, OR_E_SC_DIEL_TIR); }
+      else OR_EVENT(C, OR_E_SC_DIEL_REFRACT);
       out->d = dir;
       return 1;
     }
@@ -785,20 +818,42 @@ static int scatter_eval(const rp_scatter* sc, const ray_t* in, const hit_t* h, o
 
 /* ---- integrator (render.rs:94-146) ---- */
 
+#ifndef OR_NO_EVENT_COUNTERS
+/* census of one path vertex: before shading (hit kind, texture context) and after it (emit kinds, texture pairs) */
+static void census_begin(ctr_t* C, const hitm_t* h) {
+  C->ntex = C->nimg = 0;
+  if (!h) { C->c[OR_E_HIT_MISS]++; C->where = OR_E_TX_ON_MISS; return; }
+  C->c[h->ekind]++;
+  if (h->ekind == OR_E_HIT_TRI && h->emesh >= 1) C->c[OR_E_HIT_TRI_MESH1]++;
+  C->where = h->ekind == OR_E_HIT_TRI ? OR_E_TX_ON_TRI : OR_E_TX_ON_SPH;
+}
+static void census_end(ctr_t* C, const rp_emit* e, int background, int scattered) {
+  C->c[(background ? OR_E_BG_NONE : OR_E_EM_NONE) + e->kind]++;
+  if (!background && scattered && e->kind != RP_EMIT_NONE) C->c[OR_E_EMS_DEBUG_NORMALS + (e->kind - 1)]++;
+  if (C->ntex >= 2) C->c[OR_E_HIT_TWO_TEX]++;
+  if (C->nimg >= 2) C->c[OR_E_HIT_TWO_IMG]++;
+}
+#endif
+
 static v3 trace_continue(const or_scene* s, const ray_t* ray, uint32_t depth, or_rng* rng, ctr_t* C) {
-  if (depth == 0) return V(0.0, 0.0, 0.0);
+  if (depth == 0) { OR_EVENT(C, OR_E_DEPTH_OUT); return V(0.0, 0.0, 0.0); }
   hitm_t h = scene_hit(s, ray, C);
   if (h.valid) {
     const rp_material* m = &s->mat[h.material];
     ray_t sc;
-    int scattered = scatter_eval(&m->scatter, ray, &h.h, rng, &sc);
+    OR_CENSUS(census_begin(C, &h));
+    int scattered = scatter_eval(&m->scatter, ray, &h.h, rng, &sc, C);
     v3 absorb = absorb_eval(s, &m->absorb, &h.h, C);
     v3 emit = emit_eval(s, &m->emit, ray, &h.h, C);
+    OR_CENSUS(census_end(C, &m->emit, 0, scattered));
     if (!scattered) return add(emit, V(0.0, 0.0, 0.0));
     return add(emit, mulc(absorb, trace_continue(s, &sc, depth - 1, rng, C)));
   }
   hit_t inf = hit_at_infinity(ray->d);
-  return emit_eval(s, &s->background, ray, &inf, C);
+  OR_CENSUS(census_begin(C, NULL));
+  v3 bg = emit_eval(s, &s->background, ray, &inf, C);
+  OR_CENSUS(census_end(C, &s->background, 1, 0));
+  return bg;
 }
 
 static v3 trace_first(const or_scene* s, const ray_t* ray, uint32_t depth, or_rng* rng, ctr_t* C, int* hit_flag) {
@@ -806,16 +861,21 @@ static v3 trace_first(const or_scene* s, const ray_t* ray, uint32_t depth, or_rn
   if (h.valid) {
     const rp_material* m = &s->mat[h.material];
     ray_t sc;
-    int scattered = scatter_eval(&m->scatter, ray, &h.h, rng, &sc);
+    OR_CENSUS(census_begin(C, &h));
+    int scattered = scatter_eval(&m->scatter, ray, &h.h, rng, &sc, C);
     v3 absorb = absorb_eval(s, &m->absorb, &h.h, C);
     v3 emit = emit_eval(s, &m->emit, ray, &h.h, C);
+    OR_CENSUS(census_end(C, &m->emit, 0, scattered));
     *hit_flag = 1;
     if (!scattered) return add(emit, V(0.0, 0.0, 0.0));
     return add(emit, mulc(absorb, trace_continue(s, &sc, depth - 1, rng, C)));
   }
   *hit_flag = 0;
   hit_t inf = hit_at_infinity(ray->d);
-  return emit_eval(s, &s->background, ray, &inf, C);
+  OR_CENSUS(census_begin(C, NULL));
+  v3 bg = emit_eval(s, &s->background, ray, &inf, C);
+  OR_CENSUS(census_end(C, &s->background, 1, 0));
+  return bg;
 }
 
 /* render.rs:32-52 Camera::shoot */
@@ -862,6 +922,7 @@ typedef struct {
   const rp_render_params* p;
   double* out;
   float* fg;
+  uint64_t* mask;  /* nullable: per pixel, bit (k - OR_E_FIRST) set when its samples produced event k */
   uint32_t tiles_x, n_tiles, tw, th, shards, shard;
   uint32_t next_tile;
   pthread_mutex_t mu;
@@ -891,6 +952,7 @@ static void* render_worker(void* arg) {
         const uint64_t WH = (uint64_t)J->p->width * J->p->height;
         const uint64_t N = J->p->samples_per_stream ? J->p->samples_per_stream : OR_SAMPLES_PER_STREAM;
         double c[3] = {0.0, 0.0, 0.0}, fg = 0.0;
+        const ctr_t before = C;
         for (uint64_t b = 0; b * N < J->p->spp; b++) {
           uint64_t n = J->p->spp - b * N;
           if (n > N) n = N;
@@ -905,6 +967,12 @@ static void* render_worker(void* arg) {
         size_t px = (size_t)j * J->p->width + i;
         J->out[3 * px] = c[0] / spp; J->out[3 * px + 1] = c[1] / spp; J->out[3 * px + 2] = c[2] / spp;
         if (J->fg) J->fg[px] = (float)(fg / spp);
+        if (J->mask) {
+          uint64_t m = 0;
+          for (int k = OR_E_FIRST; k < OR_C_N; k++)
+            if (C.c[k] != before.c[k]) m |= 1ull << (k - OR_E_FIRST);
+          J->mask[px] = m;
+        }
       }
   }
   pthread_mutex_lock(&J->mu);
@@ -913,12 +981,12 @@ static void* render_worker(void* arg) {
   return NULL;
 }
 
-int or_render(or_scene* s, const rp_camera* cam, const rp_render_params* p, double* out_rgb, float* out_fg,
-              uint64_t* counters, int threads) {
+static int render_frame(or_scene* s, const rp_camera* cam, const rp_render_params* p, double* out_rgb, float* out_fg,
+                        uint64_t* counters, int n_counters, uint64_t* out_mask, int threads) {
   if (!s || !cam || !p || !out_rgb || p->max_bounce < 1 || p->width == 0 || p->height == 0) return -1;
   job_t J;
   memset(&J, 0, sizeof J);
-  J.s = s; J.cam = cam; J.p = p; J.out = out_rgb; J.fg = out_fg;
+  J.s = s; J.cam = cam; J.p = p; J.out = out_rgb; J.fg = out_fg; J.mask = out_mask;
   J.tw = p->tile_w ? p->tile_w : 32; J.th = p->tile_h ? p->tile_h : 32;
   J.tiles_x = (p->width + J.tw - 1) / J.tw;
   J.n_tiles = J.tiles_x * ((p->height + J.th - 1) / J.th);
@@ -931,8 +999,18 @@ int or_render(or_scene* s, const rp_camera* cam, const rp_render_params* p, doub
   for (int t = 0; t < threads; t++) pthread_join(th[t], NULL);
   free(th);
   pthread_mutex_destroy(&J.mu);
-  if (counters) for (int k = 0; k < OR_C_N; k++) counters[k] += J.total.c[k];
+  if (counters) for (int k = 0; k < n_counters; k++) counters[k] += J.total.c[k];
   return 0;
+}
+
+int or_render(or_scene* s, const rp_camera* cam, const rp_render_params* p, double* out_rgb, float* out_fg,
+              uint64_t* counters, int threads) {
+  return render_frame(s, cam, p, out_rgb, out_fg, counters, OR_C_N_BASE, NULL, threads);
+}
+
+int or_render_events(or_scene* s, const rp_camera* cam, const rp_render_params* p, double* out_rgb, float* out_fg,
+                     uint64_t* counters, uint64_t* out_mask, int threads) {
+  return render_frame(s, cam, p, out_rgb, out_fg, counters, OR_C_N, out_mask, threads);
 }
 
 /* ---- the reference driver for the CPU baseline (main.rs:36-106) ---- */
@@ -1022,7 +1100,7 @@ double or_render_baseline(or_scene* s, const rp_camera* cam, uint32_t width, uin
   free(th);
   free(B.q);
   pthread_mutex_destroy(&B.mu);
-  if (counters) for (int k = 0; k < OR_C_N; k++) counters[k] += B.total.c[k];
+  if (counters) for (int k = 0; k < OR_C_N_BASE; k++) counters[k] += B.total.c[k];
   return el;
 }
 

@@ -57,7 +57,38 @@ void or_lookat(const double position[3], const double target[3], const double up
 typedef struct or_scene or_scene;
 
 /* counters[0..4] = {rays (root hit calls), aabb tests, triangle tests, sphere tests, samples} */
-enum { OR_C_RAYS = 0, OR_C_BOX, OR_C_TRI, OR_C_SPH, OR_C_SAMPLES, OR_C_TRI_HITS, OR_C_TEXELS, OR_C_N };
+enum {
+  OR_C_RAYS = 0, OR_C_BOX, OR_C_TRI, OR_C_SPH, OR_C_SAMPLES, OR_C_TRI_HITS, OR_C_TEXELS,
+  OR_C_N_BASE,  /* or_intersect, or_render and or_render_baseline write counters[0 .. OR_C_N_BASE) */
+
+  /* ---- the shading census: which branch of the shading each path vertex took.  Counted through OR_EVENT
+   * like the per-event counters above (the timed baseline build compiles none of it), reported by
+   * or_render_events only.  One path vertex = one closest-hit query and the shading of its result. ---- */
+  OR_E_FIRST = OR_C_N_BASE,
+  /* what the closest-hit query returned; TRI_MESH1: a triangle of a mesh with index >= 1 (also counted as TRI) */
+  OR_E_HIT_TRI = OR_E_FIRST, OR_E_HIT_SPH, OR_E_HIT_MISS, OR_E_HIT_TRI_MESH1,
+  /* Scatter::evaluate (material.rs:115-179).  DIEL_INSIDE is counted besides the outcome of the same vertex
+   * (REFLECT: the Bernoulli draw chose reflection; TIR: refract returned none; REFRACT) */
+  OR_E_SC_NONE, OR_E_SC_LAMBERT, OR_E_SC_LAMBERT_BACK, OR_E_SC_METAL, OR_E_SC_METAL_BACK, OR_E_SC_METAL_BELOW,
+  OR_E_SC_DIEL_INSIDE, OR_E_SC_DIEL_REFLECT, OR_E_SC_DIEL_REFRACT, OR_E_SC_DIEL_TIR,
+  OR_E_DEPTH_OUT,  /* trace_continue entered with depth 0 */
+  /* Absorb::evaluate, in RP_ABSORB_* order */
+  OR_E_AB_BLACK_BODY, OR_E_AB_WHITE_BODY, OR_E_AB_ALBEDO, OR_E_AB_ALBEDO_MAP,
+  /* Emit::evaluate of a hit's material, in RP_EMIT_* order; EMS: the same on a surface that scattered */
+  OR_E_EM_NONE, OR_E_EM_DEBUG_NORMALS, OR_E_EM_COLOR, OR_E_EM_SKY_GRADIENT, OR_E_EM_SKY_SPHERE,
+  OR_E_EMS_DEBUG_NORMALS, OR_E_EMS_COLOR, OR_E_EMS_SKY_GRADIENT, OR_E_EMS_SKY_SPHERE,
+  /* Emit::evaluate of the background, in RP_EMIT_* order */
+  OR_E_BG_NONE, OR_E_BG_DEBUG_NORMALS, OR_E_BG_COLOR, OR_E_BG_SKY_GRADIENT, OR_E_BG_SKY_SPHERE,
+  /* Texture::sample, counted where it evaluates: every node of a Checker chain counts */
+  OR_E_TX_MISSING, OR_E_TX_DEBUG_UVS, OR_E_TX_SOLID, OR_E_TX_IMAGE, OR_E_TX_NOISE, OR_E_TX_PERLIN,
+  OR_E_TX_CHECKER_EVEN, OR_E_TX_CHECKER_ODD,
+  OR_E_TX_CHECKER_IN_CHECKER, OR_E_TX_IMAGE_IN_CHECKER,  /* reached through a Checker */
+  OR_E_TX_CLAMP_X_LO, OR_E_TX_CLAMP_X_HI, OR_E_TX_CLAMP_Y_LO, OR_E_TX_CLAMP_Y_HI,  /* Image clamps taken */
+  /* a material's or the background's texture evaluated at a triangle hit / a sphere hit / a miss */
+  OR_E_TX_ON_TRI, OR_E_TX_ON_SPH, OR_E_TX_ON_MISS,
+  OR_E_HIT_TWO_TEX, OR_E_HIT_TWO_IMG,  /* one hit evaluated two textures (Absorb and Emit) / two Images */
+  OR_C_N
+};
 
 or_scene* or_scene_create(const rp_scene_desc* desc);  /* builds the reference median-split BVH */
 void or_scene_destroy(or_scene* s);
@@ -75,6 +106,11 @@ int or_intersect(or_scene* s, const double* rays, uint64_t n, double* out_hit, u
  * threads >= 1; the result does not depend on it. */
 int or_render(or_scene* s, const rp_camera* cam, const rp_render_params* p, double* out_rgb,
               float* out_fg, uint64_t* counters, int threads);
+
+/* or_render that also reports the shading census: counters[0 .. OR_C_N), and, when out_mask is not NULL, per
+ * pixel (j * width + i) the mask of the census events its samples produced: bit (k - OR_E_FIRST) for event k. */
+int or_render_events(or_scene* s, const rp_camera* cam, const rp_render_params* p, double* out_rgb,
+                     float* out_fg, uint64_t* counters, uint64_t* out_mask, int threads);
 
 /* The reference driver (main.rs:36-106): LIFO tile queue behind a mutex, `workers` threads each with its
  * own StdRng (seed_from_u64(seed + worker) in place of from_entropy), recursive trace_path.  Returns the

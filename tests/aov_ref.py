@@ -27,11 +27,20 @@ FRAMES = {"variants": (64, 48), "earth": (64, 48), "variants_sky": (64, 48), "th
 PINHOLE = ("variants", "earth", "variants_sky", "bunny_full")
 
 
+def add_frame(name: str, scene, width: int, height: int) -> None:
+    """Enter a scene object (not of the catalogue) into the frame table under `name`."""
+    FRAMES[name] = (width, height, scene)
+
+
+def _pinhole(name: str) -> bool:
+    return name in PINHOLE or (len(FRAMES[name]) == 3 and FRAMES[name][2].camera.lens_radius == 0.0)
+
+
 def scene_params(name: str, spp: int, **kw):
     from rtpotato import scenes
     from rtpotato.scene import RenderParams
-    w, h = FRAMES[name]
-    sc = scenes.configure(scenes.CATALOGUE[name](), w, h)
+    w, h = FRAMES[name][:2]
+    sc = scenes.configure(FRAMES[name][2] if len(FRAMES[name]) == 3 else scenes.CATALOGUE[name](), w, h)
     return sc, RenderParams(w, h, spp, 8, SEED, 32, 32, **kw)
 
 
@@ -148,7 +157,7 @@ def refs(name: str, spp: int) -> dict:
         albedo, fg_b = albedo_ref(sc, p)
         assert np.array_equal(fg, fg_b)
         out = {"scene": sc, "params": p, "normal": normal, "albedo": albedo, "fg": fg}
-        if name in PINHOLE:
+        if _pinhole(name):
             out["depth"], out["depth_fg"], out["depth_normal"] = depth_ref(sc, p)
         for v in out.values():
             if isinstance(v, np.ndarray):

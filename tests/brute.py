@@ -15,13 +15,25 @@ class Brute:
         self.sph_id = np.nonzero(root["kind"] == 0)[0]
         tri = root[self.tri_id]
         if len(tri):
-            assert len(sd.mesh_table) == 1
-            m = sd.mesh_table[0]
-            self.mesh = m
-            idx = m.indices.reshape(-1)
+            # per triangle: its mesh, and the corners' positions, normals and uvs out of that mesh's own arrays
+            self.tri_mesh = tri["mesh"].astype(np.int64)
             t0 = tri["triangle"].astype(np.int64)
-            self.ia, self.ib, self.ic = idx[t0], idx[t0 + 1], idx[t0 + 2]
-            self.A, B, C = m.positions[self.ia], m.positions[self.ib], m.positions[self.ic]
+            n = len(tri)
+            corner = np.zeros((3, n), dtype=np.int64)
+            pos, self.nrm, self.uv = np.zeros((3, n, 3)), np.zeros((3, n, 3)), np.zeros((3, n, 2))
+            self.tri_mat = np.zeros(n, dtype=np.uint32)
+            for mi, m in enumerate(sd.mesh_table):
+                of = self.tri_mesh == mi
+                idx = m.indices.reshape(-1)
+                for c in range(3):
+                    corner[c, of] = idx[t0[of] + c]
+                    pos[c, of], self.nrm[c, of], self.uv[c, of] = (m.positions[corner[c, of]], m.normals[corner[c, of]],
+                                                                   m.uvs[corner[c, of]])
+                self.tri_mat[of] = m.material
+            self.ia, self.ib, self.ic = corner  # vertex indices within each triangle's own mesh
+            if len(sd.mesh_table) == 1:
+                self.mesh = sd.mesh_table[0]
+            self.A, B, C = pos
             self.ba, self.ca = self.A - B, self.A - C
         self.sph = [(np.array(h["center"], dtype=np.float64), float(h["radius"]), int(h["material"]))
                     for h in root[self.sph_id]]
@@ -89,3 +101,34 @@ class Brute:
             out["v"][s:s + chunk] = np.where(hit, V[rows, j], 0.0)
             out["tie"][s:s + chunk] = hit & ((T == best[:, None]).sum(axis=1) > 1)
         return out
+
+    def records(self, rays, ref):
+        """The reference's Hit records of closest()'s result `ref`: (rec (n, 9) {t, position, normal, uv}, material
+        (n,) u32 -- 0xFFFFFFFF on a miss --, is_tri (n,) bool), recomputed from (hittable, t, u, v) in the reference's
+        expression order (hittable.rs:54-62, 95-107), every triangle out of its own mesh."""
+        n = len(rays)
+        o, d, t = rays[:, 0:3], rays[:, 3:6], ref["t"]
+        hit = ref["id"] >= 0
+        rec = np.zeros((n, 9))
+        rec[:, 0] = np.where(hit, t, np.inf)
+        mats = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = o + t[:, None] * d
+        is_tri = hit & np.isin(ref["id"], self.tri_id)
+        if is_tri.any():
+            k = np.searchsorted(self.tri_id, np.where(is_tri, ref["id"], self.tri_id[0]))
+            u, v = ref["u"][:, None], ref["v"][:, None]
+            w = 1.0 - u - v
+            nt = (w * self.nrm[0][k] + u * self.nrm[1][k]) + v * self.nrm[2][k]
+            uvt = (w * self.uv[0][k] + u * self.uv[1][k]) + v * self.uv[2][k]
+            rec[is_tri, 1:4], rec[is_tri, 4:7], rec[is_tri, 7:9] = p[is_tri], nt[is_tri], uvt[is_tri]
+            mats[is_tri] = self.tri_mat[k][is_tri]
+        for q, (c, rad, mat) in enumerate(self.sph):
+            s = hit & (ref["id"] == self.sph_id[q])
+            pc = p[s] - c[None]
+            ns = pc / np.sqrt((pc[:, 0] * pc[:, 0] + pc[:, 1] * pc[:, 1]) + pc[:, 2] * pc[:, 2])[:, None]
+            rec[s, 1:4], rec[s, 4:7] = p[s], ns
+            rec[s, 7] = 0.5 - np.arctan2(ns[:, 2], ns[:, 0]) / (2.0 * np.pi)
+            rec[s, 8] = np.arcsin(ns[:, 1]) / np.pi + 0.5
+            mats[s] = mat
+        return rec, mats, is_tri

@@ -1,7 +1,9 @@
 """Independent restatement (pure Python + numpy elementwise f64) of the reference's hot path, used to
 generate the golden fixtures that pin the C oracle (tests/test_oracle_golden.py).  Test infrastructure.
 
-    python tests/golden/make_golden.py     ->  tests/golden/golden.npz
+    python tests/golden/make_golden.py            ->  tests/golden/golden.npz
+    python tests/golden/make_golden.py shading    ->  tests/golden/golden_shading.npz  (tests/shading_scenes.py's
+                                                      aimed scenes: several meshes; tests/test_shading_census.py)
 
 Written from the Rust sources (/root/reference/src), not from oracle/rp_oracle.c: Python floats and
 numpy f64 elementwise ops are IEEE binary64 with no FMA contraction, math.tan/atan2/asin/sqrt call the
@@ -174,13 +176,19 @@ class PyScene:
         tri = root[root["kind"] == 1]
         sph = root[root["kind"] == 0]
         self.order = np.nonzero(root["kind"] == 1)[0].tolist() + np.nonzero(root["kind"] == 0)[0].tolist()
-        m = sd.mesh_table[0] if len(tri) else None
-        self.mesh = m
         if len(tri):
-            idx = m.indices.reshape(-1)
+            # per triangle: its mesh (hittable.rs:13 Triangle(TriangleId, MeshId)) and the three vertices' positions,
+            # normals and uvs out of that mesh's own arrays (mesh.rs:25-30)
+            self.tri_mesh = tri["mesh"].astype(np.int64)
             t0 = tri["triangle"].astype(np.int64)
-            self.ia, self.ib, self.ic = idx[t0], idx[t0 + 1], idx[t0 + 2]
-            self.A, self.B, self.C = m.positions[self.ia], m.positions[self.ib], m.positions[self.ic]
+            corners = []
+            for c in range(3):
+                vi = [int(sd.mesh_table[m].indices.reshape(-1)[t + c]) for m, t in zip(self.tri_mesh, t0)]
+                corners.append((np.array([sd.mesh_table[m].positions[v] for m, v in zip(self.tri_mesh, vi)]),
+                                [tuple(sd.mesh_table[m].normals[v]) for m, v in zip(self.tri_mesh, vi)],
+                                [tuple(sd.mesh_table[m].uvs[v]) for m, v in zip(self.tri_mesh, vi)]))
+            (self.A, self.nA, self.uvA), (self.B, self.nB, self.uvB), (self.C, self.nC, self.uvC) = corners
+            self.tri_mat = [int(sd.mesh_table[m].material) for m in self.tri_mesh]
         else:
             self.A = np.zeros((0, 3))
         self.sph = [(tuple(h["center"]), float(h["radius"]), int(h["material"])) for h in sph]
@@ -243,12 +251,11 @@ class PyScene:
         if best[0] == "t":
             k, u, v = best[1], best[2], best[3]
             w = 1.0 - u - v
-            m = self.mesh
-            n0, n1, n2 = (tuple(m.normals[i]) for i in (self.ia[k], self.ib[k], self.ic[k]))
-            uv0, uv1, uv2 = (tuple(m.uvs[i]) for i in (self.ia[k], self.ib[k], self.ic[k]))
+            n0, n1, n2 = self.nA[k], self.nB[k], self.nC[k]
+            uv0, uv1, uv2 = self.uvA[k], self.uvB[k], self.uvC[k]
             n = add(add(smul(w, n0), smul(u, n1)), smul(v, n2))
             uv = ((w * uv0[0] + u * uv1[0]) + v * uv2[0], (w * uv0[1] + u * uv1[1]) + v * uv2[1])
-            mat = m.material
+            mat = self.tri_mat[k]
         else:
             c, r, mat = self.sph[best[1]]
             n = normalize(sub(p, c))
@@ -439,5 +446,26 @@ def main():
     np.savez_compressed(os.path.join(HERE, "golden.npz"), **out)
 
 
+SHADING_SIZE = (24, 16, 4)  # width, height, spp of the aimed scenes' frames in golden_shading.npz
+
+
+def main_shading():
+    """python tests/golden/make_golden.py shading  ->  tests/golden/golden_shading.npz: small frames and ray counts
+    of the aimed shading scenes (tests/shading_scenes.py).  golden.npz is left alone."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import shading_scenes as S
+    from rtpotato import scenes
+    W, H, spp = SHADING_SIZE
+    out = {}
+    for name in S.SCENES:
+        sc = scenes.configure(S.scene(name), W, H)
+        img, rays_n = PyScene(sc).render(W, H, spp, S.SEED, S.params(name).max_bounce)
+        out[f"img_{name}"] = img
+        out[f"img_{name}_rays"] = np.array([rays_n])
+        out[f"img_{name}_size"] = np.array([W, H, spp])
+        print(name, img.mean(axis=(0, 1)), rays_n, flush=True)
+    np.savez_compressed(os.path.join(HERE, "golden_shading.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    main_shading() if sys.argv[1:] == ["shading"] else main()

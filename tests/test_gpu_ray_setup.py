@@ -114,31 +114,8 @@ def reference():
     rays = _rays(scene)
     bf = Brute(scene)
     ref = bf.closest(rays)
-    n = len(rays)
-    o, d, t = rays[:, 0:3], rays[:, 3:6], ref["t"]
+    rec, mats, is_tri = bf.records(rays, ref)
     hit = ref["id"] >= 0
-    rec = np.zeros((n, 9))
-    rec[:, 0] = np.where(hit, t, np.inf)
-    with np.errstate(invalid="ignore", over="ignore"):
-        p = o + t[:, None] * d
-    m = bf.mesh
-    is_tri = hit & np.isin(ref["id"], bf.tri_id)
-    k = np.searchsorted(bf.tri_id, np.where(is_tri, ref["id"], bf.tri_id[0]))
-    u, v = ref["u"][:, None], ref["v"][:, None]
-    w = 1.0 - u - v
-    nt = (w * m.normals[bf.ia[k]] + u * m.normals[bf.ib[k]]) + v * m.normals[bf.ic[k]]
-    uvt = (w * m.uvs[bf.ia[k]] + u * m.uvs[bf.ib[k]]) + v * m.uvs[bf.ic[k]]
-    mats = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
-    mats[is_tri] = m.material
-    rec[is_tri, 1:4], rec[is_tri, 4:7], rec[is_tri, 7:9] = p[is_tri], nt[is_tri], uvt[is_tri]
-    for q, (c, rad, mat) in enumerate(bf.sph):
-        s = hit & (ref["id"] == bf.sph_id[q])
-        pc = p[s] - c[None]
-        ns = pc / np.sqrt((pc[:, 0] * pc[:, 0] + pc[:, 1] * pc[:, 1]) + pc[:, 2] * pc[:, 2])[:, None]
-        rec[s, 1:4], rec[s, 4:7] = p[s], ns
-        rec[s, 7] = 0.5 - np.arctan2(ns[:, 2], ns[:, 0]) / (2.0 * np.pi)
-        rec[s, 8] = np.arcsin(ns[:, 1]) / np.pi + 0.5
-        mats[s] = mat
     out = {"rec": rec, "mats": mats, "hit": hit, "tri": is_tri, "tie": ref["tie"].copy()}
     for a in out.values():
         a.setflags(write=False)

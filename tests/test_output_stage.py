@@ -104,3 +104,43 @@ def test_shard_to_bgra8_matches_host(gpu):
                                     rgba.ctypes.data)
             assert tga_bytes(params.width, params.height, frame) == tga_bytes(params.width, params.height,
                                                                               rgba[..., [2, 1, 0, 3]])
+
+
+@pytest.mark.gpu
+def test_shard_to_bgra8_on_the_edge_values(gpu):
+    """srgb_bgra_kernel itself on the values test_lookup_equals_to_srgb_u8 feeds the numpy emulation of its search:
+    every threshold and both its neighbours, k/255, (k/255)^2.2 and their neighbours, NaN, +-inf, -0.0, 5e-324,
+    +-1e300 and random values, as the shard buffer of a 160 x 112 frame in 16 x 16 tiles (17,920 slots, 53,760
+    channels: 1,798 edge values and 51,962 random ones, shuffled so every edge value meets every channel position).
+    Byte for byte rph_to_srgb_u8 of the same buffer, B, G, R, A."""
+    import torch
+    from rtpotato import _ffi as F
+    from rtpotato import scenes
+    from rtpotato.render import srgb_thresholds
+    from rtpotato.scene import RenderParams, shard_slot_count
+    params = RenderParams(160, 112, 1, 8, 1, 16, 16)
+    n = shard_slot_count(params)
+    assert n == 17920
+    thr = srgb_thresholds()
+    rng = np.random.default_rng(213)
+    k = np.arange(256) / 255.0
+    edge = np.concatenate([
+        thr[1:], np.nextafter(thr[1:], -np.inf), np.nextafter(thr[1:], np.inf),
+        k, k ** 2.2, np.nextafter(k ** 2.2, np.inf), np.nextafter(k ** 2.2, -np.inf),
+        [0.0, -0.0, 1.0, np.nan, np.inf, -np.inf, 5e-324, 1e300, -1e300],
+    ])
+    m = 3 * n - len(edge)
+    x = np.concatenate([edge, rng.uniform(-0.2, 1.3, m - 10_000), 10.0 ** rng.uniform(-12, 0, 10_000)])
+    assert len(edge) == 1798 and x.size == 3 * n
+    x = np.ascontiguousarray(rng.permutation(x))
+    ref = np.zeros((n, 4), dtype=np.uint8)
+    F.host().rph_to_srgb_u8(x.ctypes.data, n, ref.ctypes.data)
+    rgb = torch.from_numpy(x).cuda()
+    out = torch.full((4 * n,), 7, dtype=torch.uint8, device="cuda")
+    with gpu.DeviceScene(scenes.three_balls()) as ds:
+        ds.to_bgra8(params, rgb, out)
+        torch.cuda.synchronize()
+    got = out.cpu().numpy().reshape(n, 4)
+    bad = np.nonzero((got != ref[:, [2, 1, 0, 3]]).any(axis=1))[0]
+    assert len(bad) == 0, (bad[:8], x.reshape(n, 3)[bad[:8]], got[bad[:8]], ref[bad[:8]])
+    assert len(np.unique(ref[:, :3])) == 256

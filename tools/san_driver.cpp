@@ -268,6 +268,12 @@ static void check_oracle_render(const MeshScene& s) {
   CHECK(or_render(os, &cam, &rp, b.data(), nullptr, cb, 8) == 0);
   CHECK(std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0);
   CHECK(ca[OR_C_RAYS] == cb[OR_C_RAYS]);
+  // the same frame with the shading census: all OR_C_N counters and the per-pixel event mask, 8 threads
+  std::vector<uint64_t> mask(48 * 32, 0);
+  uint64_t ce[OR_C_N] = {0};
+  CHECK(or_render_events(os, &cam, &rp, b.data(), nullptr, ce, mask.data(), 8) == 0);
+  CHECK(std::memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0);
+  CHECK(ce[OR_C_RAYS] == ca[OR_C_RAYS] && ce[OR_E_HIT_TRI] + ce[OR_E_HIT_SPH] + ce[OR_E_HIT_MISS] == ce[OR_C_RAYS]);
   const double secs = or_render_baseline(os, &cam, 32, 32, 2, 8, 16, 8, 11, nullptr, ca);
   CHECK(secs >= 0.0);
   or_scene_destroy(os);
