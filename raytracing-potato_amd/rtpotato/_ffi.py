@@ -132,6 +132,45 @@ def hittable_dtype():
                      "offsets": [0, 4, 8, 12, 16, 40], "itemsize": 48})
 
 
+# numpy dtypes with exactly the layouts of csrc/rp_layout.h's records (rp_scene_tree; DeviceScene.tree())
+def node4_dtype():
+    import numpy as np
+    names = ["lo_x", "hi_x", "lo_y", "hi_y", "lo_z", "hi_z"]
+    return np.dtype({"names": names + ["child", "pad"], "formats": [("<f4", (4,))] * 6 + [("<u4", (4,))] * 2,
+                     "offsets": [16 * k for k in range(8)], "itemsize": 128})
+
+
+def node4q_dtype():
+    import numpy as np
+    names = ["lo_x", "hi_x", "lo_y", "hi_y", "lo_z", "hi_z"]
+    return np.dtype({"names": ["o", "s"] + names + ["child"],
+                     "formats": [("<f4", (3,))] * 2 + [("u1", (4,))] * 6 + [("<u4", (4,))],
+                     "offsets": [0, 12] + [24 + 4 * k for k in range(6)] + [48], "itemsize": 64})
+
+
+def node8q_dtype():
+    import numpy as np
+    names = ["lo_x", "hi_x", "lo_y", "hi_y", "lo_z", "hi_z"]
+    return np.dtype({"names": ["o", "s", "inner", "prim"] + names + ["pmask", "pad"],
+                     "formats": [("<f4", (3,))] * 2 + ["<u4", "<u4"] + [("u1", (8,))] * 6 + [("<u4", (8,)), ("<u4", (4,))],
+                     "offsets": [0, 12, 24, 28] + [32 + 8 * k for k in range(6)] + [80, 112], "itemsize": 128})
+
+
+def prim_dtype():
+    import numpy as np
+    return np.dtype({"names": ["g", "kind", "material"], "formats": [("<f8", (9,)), "<u4", "<u4"],
+                     "offsets": [0, 72, 76], "itemsize": 80})
+
+
+def prim_ref_dtype():
+    import numpy as np
+    return np.dtype({"names": ["v", "src"], "formats": [("<u4", (3,)), "<u4"], "offsets": [0, 12], "itemsize": 16})
+
+
+def node_dtype(node_format: int):
+    return {RP_NODES_F32: node4_dtype, RP_NODES_Q8: node4q_dtype, RP_NODES_W8: node8q_dtype}[node_format]()
+
+
 class RPError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"rp error {code}: {message}")
@@ -155,7 +194,7 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_denoise_device", "rp_denoise", "rp_render_variance_device_ws", "rp_denoise_var_params_init",
               "rp_denoise_var_scratch_bytes", "rp_denoise_var_device", "rp_denoise_var", "rp_accum_frames_device",
               "rp_accum_error_device_ws", "rp_render_tiles_device_ws", "rp_accum_tiles_select_device",
-              "rp_accum_frames_tiles_device"]
+              "rp_accum_frames_tiles_device", "rp_scene_tree"]
 class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
     _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
                 ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
@@ -284,6 +323,8 @@ def rp() -> ctypes.CDLL:
                                                  c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.rp_accum_frames_tiles_device.argtypes = [c_uint64, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p,
                                                  c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.rp_scene_tree.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint32),
+                                  POINTER(c_uint32)]
     if lib.rp_abi_version() != RP_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rp_abi_version()}, bindings expect {RP_ABI_VERSION} (rebuild)")
     _rp = lib

@@ -68,6 +68,20 @@ class DeviceScene:
         return {"nodes": nn.value, "leaves": nl.value, "max_depth": md.value, "prims": np_.value,
                 "device_bytes": nb.value}
 
+    def tree(self) -> dict:
+        """rp_scene_tree (a test hook): the packed tree as it lies in device memory.  "nodes": a structured array of
+        Node4, Node4Q or Node8Q records by "node_format" (RP_NODES_*; _ffi.node_dtype), "prims" and "prim_refs" in leaf
+        order (_ffi.prim_dtype, prim_ref_dtype), "root": the root's node index."""
+        fmt, root = ctypes.c_uint32(), ctypes.c_uint32()
+        F.check(F.rp().rp_scene_tree(self.handle, None, 0, None, 0, None, 0, ctypes.byref(fmt), ctypes.byref(root)))
+        info = self.info()
+        nodes = np.zeros(info["nodes"], dtype=F.node_dtype(fmt.value))
+        prims = np.zeros(info["prims"], dtype=F.prim_dtype())
+        refs = np.zeros(info["prims"], dtype=F.prim_ref_dtype())
+        F.check(F.rp().rp_scene_tree(self.handle, nodes.ctypes.data, nodes.nbytes, prims.ctypes.data, prims.nbytes,
+                                     refs.ctypes.data, refs.nbytes, None, None))
+        return {"node_format": fmt.value, "root": root.value, "nodes": nodes, "prims": prims, "prim_refs": refs}
+
     def build_times(self) -> dict:
         """rp_scene_build_times: host seconds of the scene_create phases."""
         t = np.zeros(6)

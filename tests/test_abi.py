@@ -74,6 +74,42 @@ int main(void) {
     assert F.hittable_dtype().itemsize == ctypes.sizeof(F.rp_hittable)
 
 
+def test_tree_record_dtypes_match_rp_layout(tmp_path):
+    """The numpy dtypes DeviceScene.tree() returns have the sizes of rp_layout.h's static_asserts (Node4 128, Node4Q 64,
+    Node8Q 128, Prim 80, PrimRef 16) and the fields' offsets (a tiny C++ program over the header itself)."""
+    from rtpotato import _ffi as F
+    code = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "rp_layout.h"
+using namespace rpl;
+int main() {
+  printf("%zu %zu %zu %zu %zu\n", sizeof(Node4), sizeof(Node4Q), sizeof(Node8Q), sizeof(Prim), sizeof(PrimRef));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", offsetof(Node4, lo_x), offsetof(Node4, hi_x), offsetof(Node4, lo_y),
+         offsetof(Node4, hi_y), offsetof(Node4, lo_z), offsetof(Node4, hi_z), offsetof(Node4, child), offsetof(Node4, pad));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", offsetof(Node4Q, o), offsetof(Node4Q, s), offsetof(Node4Q, lo_x),
+         offsetof(Node4Q, hi_x), offsetof(Node4Q, lo_y), offsetof(Node4Q, hi_y), offsetof(Node4Q, lo_z),
+         offsetof(Node4Q, hi_z), offsetof(Node4Q, child));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", offsetof(Node8Q, o), offsetof(Node8Q, s), offsetof(Node8Q, inner),
+         offsetof(Node8Q, prim), offsetof(Node8Q, lo_x), offsetof(Node8Q, hi_x), offsetof(Node8Q, lo_y), offsetof(Node8Q, hi_y),
+         offsetof(Node8Q, lo_z), offsetof(Node8Q, hi_z), offsetof(Node8Q, pmask), offsetof(Node8Q, pad));
+  printf("%zu %zu %zu\n", offsetof(Prim, g), offsetof(Prim, kind), offsetof(Prim, material));
+  printf("%zu %zu\n", offsetof(PrimRef, v), offsetof(PrimRef, src));
+  return 0;
+}'''
+    src = tmp_path / "l.cpp"
+    src.write_text(code)
+    exe = tmp_path / "l"
+    subprocess.run(["g++", "-std=c++17", "-I", os.path.join(PKG, "csrc"), str(src), "-o", str(exe)], check=True)
+    rows = [[int(x) for x in line.split()]
+            for line in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()]
+    dts = [F.node4_dtype(), F.node4q_dtype(), F.node8q_dtype(), F.prim_dtype(), F.prim_ref_dtype()]
+    assert [d.itemsize for d in dts] == rows[0] == [128, 64, 128, 80, 16]
+    for d, offs in zip(dts, rows[1:]):
+        assert [d.fields[n][1] for n in d.names] == offs, (d, offs)
+    assert [F.node_dtype(f).itemsize for f in (F.RP_NODES_F32, F.RP_NODES_Q8, F.RP_NODES_W8)] == [128, 64, 128]
+
+
 def test_integration_rust_mirror_matches_c():
     """INTEGRATION.md's Rust #[repr(C)] mirrors of rp_render_params and rp_scene_options list the C fields in order
     (a missing trailing field would make the library read past the caller's struct)."""

@@ -122,7 +122,9 @@ def test_identical_triangles(gpu, builder, fmt, max_leaf, layout):
                          ids=[i for g, i in zip(GRID, GRID_IDS) if g[0] == "ploc"])
 def test_ploc_build_is_deterministic(gpu, fmt, max_leaf, layout):
     """Two PLOC builds of one scene: the same tree (after the depth-first relayout nothing depends on the order of the
-    collapse's atomics), so the same info() and byte-identical answers, primitive-dependent columns included."""
+    collapse's atomics), so the same info() and byte-identical answers, primitive-dependent columns included.
+    PLOC only: the LBVH has no relayout, its wide node ids come from the collapse's atomics and are not reproducible
+    (its tree is: test_gpu_bvh_ref.py compares it with the reference by a walk from the root in child slot order)."""
     n = 33
     out = []
     for _ in range(2):
