@@ -241,7 +241,7 @@ typedef struct rp_scene_options {
                                build, ~24 % slower traversal on 10 M triangles); PLOC */
   uint32_t max_leaf;        /* primitives per leaf, 1..8 (0 -> 4) */
   double cost_traverse;     /* SAH node cost relative to a primitive test (0 -> 0.7) */
-  int32_t always_max;       /* primitives tested before the tree for every ray (-1 -> 4; 0 = none) */
+  int32_t always_max;       /* most primitives tested before the tree for every ray: giant ones and, in a mesh scene with no more than this many, its spheres (-1 -> 4; 0 = none) */
   uint32_t lds_depth;       /* traversal-stack entries kept in LDS (0 -> automatic; >= 8 forces a split) */
   uint32_t self_check;      /* 1: structural self-check of a device-built tree (slow; tests) */
   uint32_t trav_threshold;  /* lanes of a wave still traversing before the finished ones shade (0 -> 24 for

@@ -67,6 +67,19 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
  * `threads` build threads (0 = the machine's, at most 16): the tree does not depend on the thread count. */
 int rph_bvh_tree_hash(const rp_scene_desc* desc, uint32_t node_format, uint32_t threads, uint64_t* hash);
 
+/* The three above with the always-tested list chosen, so the CPU model sees the tree librp.so renders with:
+ * always_max as rp_scene_options.always_max (< 0: the default, 0: every hittable in the tree), and always_minor != 0
+ * for the rule librp.so applies to every host-built tree -- a mesh scene's few non-triangle hittables are tested
+ * first for every ray too, and the tree's leaves hold triangles only (the hooks above build without it).
+ * stats (nullable) has 6 values here: {nodes, leaves, max_depth, primitives, always-tested primitives, non-triangle
+ * primitives inside the tree}. */
+int rph_bvh_selfcheck_opt(const rp_scene_desc* desc, uint32_t node_format, uint32_t collapse, int32_t always_max,
+                          uint32_t always_minor, uint64_t* stats);
+int rph_bvh_traversal_stats_opt(const rp_scene_desc* desc, const double* rays, uint64_t n, uint32_t node_format,
+                                uint32_t collapse, int32_t always_max, uint32_t always_minor, uint64_t* per_ray);
+int rph_bvh_tree_hash_opt(const rp_scene_desc* desc, uint32_t node_format, uint32_t threads, int32_t always_max,
+                          uint32_t always_minor, uint64_t* hash);
+
 /* rand 0.8 StdRng (ChaCha12, rand_chacha 0.3 stream: 64-bit block counter, zero nonce) keyed by the 32-byte
  * seed (StdRng::from_seed; seed_from_u64 seeds come from its PCG32 expansion): n consecutive next_u64
  * draws starting at draw index `first` (two keystream words each, little-endian).  Host bulk scene

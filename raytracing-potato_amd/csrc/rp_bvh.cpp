@@ -926,6 +926,21 @@ int build(const rp_scene_desc* d, const BuildOptions& opt, PackedScene& out, std
       if (std::isfinite(refs[idx[j]].box.area()) && refs[idx[j]].box.area() > 0.0 &&
           refs[idx[j]].box.area() >= opt.always_ratio * ra)
         always.push_back(idx[j]);
+    // the minor rule (BuildOptions::always_minor): a mesh scene's few non-triangle hittables join them, so every
+    // leaf of the tree holds triangles only
+    if (opt.always_minor) {
+      std::vector<uint32_t> minor;
+      uint32_t n_tri = 0;
+      for (uint32_t i = 0; i < n; i++) {
+        if (d->hittables[i].kind == RP_HITTABLE_TRIANGLE) n_tri++;
+        else if (minor.size() <= opt.always_max && std::find(always.begin(), always.end(), i) == always.end())
+          minor.push_back(i);
+      }
+      uint32_t tri_always = 0;
+      for (uint32_t a : always) tri_always += d->hittables[a].kind == RP_HITTABLE_TRIANGLE;
+      if (!minor.empty() && minor.size() + always.size() <= opt.always_max && n_tri - tri_always >= ALWAYS_MINOR_MIN_TRIS)
+        always.insert(always.end(), minor.begin(), minor.end());
+    }
     std::sort(always.begin(), always.end());
     if (!always.empty()) {
       std::vector<Ref> tree_refs;

@@ -18,6 +18,11 @@
 namespace rpb {
 
 enum : uint32_t { COLLAPSE_GREEDY = 0, COLLAPSE_SAH = 1 };
+// BuildOptions::always_minor's floor: the triangles a tree must keep for the rule to apply.  Each always-tested
+// primitive costs every ray one exact test, about what a node visit and a leaf test cost together; 16 triangles are
+// the first tree with more than one wide node of full leaves (4 children x 4 primitives), below which a ray visits the
+// root alone and a sphere in one of its leaves costs no visit.
+constexpr uint32_t ALWAYS_MINOR_MIN_TRIS = 16;
 
 struct BuildOptions {
   uint32_t max_leaf = 4;        // primitives per leaf at most (<= rpl::LEAF_MAX)
@@ -28,9 +33,17 @@ struct BuildOptions {
   bool vertex_tables = true;    // vnrm / vuv (false: the caller uploads the meshes' normals and uvs itself)
   // Primitives kept out of the tree and tested first for every ray: among the always_max largest boxes
   // (surface area), those at least always_ratio times the area of the box of everything else (config C3's
-  // ground sphere, r = 1000 under a bunny of size ~0.2).  always_max = 0 disables.
+  // ground sphere, r = 1000 under a bunny of size ~0.2).  always_max = 0 disables: every hittable is in the tree.
   uint32_t always_max = 4;
   double always_ratio = 4.0;
+  // The minor rule, applied after the size rule: in a scene with triangles whose non-triangle hittables are few --
+  // those still in the tree and the always-tested ones chosen so far number at most always_max -- and whose tree
+  // keeps at least ALWAYS_MINOR_MIN_TRIS triangles, the non-triangle hittables join the always-tested list whatever
+  // their size (C3's two small balls).  Every leaf then holds triangles only: a wave's leaf test never runs the
+  // triangle and the sphere path for one iteration, and the balls' boxes, far larger than a triangle's, stop
+  // widening the bunny's inner nodes (C3: -15 % node visits per camera ray).  Off here, so the rph_* hooks keep
+  // building the trees they built; rp_scene.cpp turns it on for every host-built tree.
+  bool always_minor = false;
   uint32_t node_format = rpl::NODES_F32;  // rpl::NODES_F32 (Node4), _Q8 (Node4Q), _W8 (Node8Q) or 0 (auto_node_format)
   uint32_t collapse = COLLAPSE_SAH;  // 4-wide collapse: COLLAPSE_GREEDY (largest-area child first) or _SAH (rp_bvh.cpp)
   uint32_t threads = 0;                   // host build threads (0 = the machine's, at most 16); same tree for any

@@ -625,7 +625,10 @@ RPK_INLINE void trav_init(const KScene& S, double tmax, TravState& t, V3 d) {
 }
 
 // One exact f64 primitive test (rp_isect.h: the reference's Hittable::hit for a leaf, hittable.rs:39-101): on
-// acceptance `best` shrinks to t and the hit record is taken.
+// acceptance `best` shrinks to t and the hit record is taken.  LEAF: a test of the leaf loop (trav_step, trav_step_w8),
+// not of the always-tested site -- the diagnostic build counts the leaf loop's sphere branch (DREG_SPHERE_PATH: the
+// iterations that run both kinds' paths); the product build compiles one text for both.
+template <bool LEAF = true>
 RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, double& best, TravState& ts) {
   // 32-bit byte offset from the wave-uniform base (scalar-base + vector-offset loads)
   const double2* q = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(S.prims) +
@@ -648,6 +651,9 @@ RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, 
     // front of the branch on the kind; with the triangle their only reader the compiler moves their loads into its
     // path, behind the wait for the kind, and a test waits for memory twice)
     asm volatile("" : : "v"(g45.x), "v"(g45.y), "v"(g67.x), "v"(g67.y), "v"(g8k.x));
+    if constexpr (LEAF) {
+      DREG(DREG_SPHERE_PATH)
+    }
     rpi::sphere_test(g0, g23.y, o, d, tmin, best, [&](double t) {
       best = t; ts.bestp = (int32_t)k; ts.bestm = mat;
     });
@@ -663,7 +669,10 @@ template <uint32_t NF>
 RPK_INLINE void trav_begin(const KScene& S, V3 o, V3 d, double tmin, double tmax, TravState& t) {
   trav_init<NF>(S, tmax, t, d);
   double best = t.best;
-  for (uint32_t k = S.always_first; k < S.always_first + S.n_always; k++) prim_test(S, k, o, d, tmin, best, t);
+  for (uint32_t k = S.always_first; k < S.always_first + S.n_always; k++) {
+    DREG(DREG_ALWAYS)
+    prim_test<false>(S, k, o, d, tmin, best, t);
+  }
   t.best = best;
 }
 

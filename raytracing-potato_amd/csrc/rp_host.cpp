@@ -557,6 +557,17 @@ int rph_bvh_traversal_stats(const rp_scene_desc* desc, const double* rays, uint6
 
 int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, uint64_t n, uint32_t node_format,
                                uint32_t collapse, uint64_t* per_ray) {
+  return rph_bvh_traversal_stats_opt(desc, rays, n, node_format, collapse, -1, 0, per_ray);
+}
+
+// rp_host.h's always_max and always_minor into the builder's options (always_max < 0: the builder's default)
+static void always_options(int32_t always_max, uint32_t always_minor, rpb::BuildOptions& bo) {
+  if (always_max >= 0) bo.always_max = (uint32_t)always_max;
+  bo.always_minor = always_minor != 0;
+}
+
+int rph_bvh_traversal_stats_opt(const rp_scene_desc* desc, const double* rays, uint64_t n, uint32_t node_format,
+                                uint32_t collapse, int32_t always_max, uint32_t always_minor, uint64_t* per_ray) {
   // CPU model of rp_device.h's traversal over the same packed tree.  The arithmetic is the kernel's source: the ray
   // setup (rp_ray.h), the frame terms, plane t^ and pass test of the conservative f32 slab test and the exact f64
   // primitive tests (rp_isect.h) -- except the reciprocal, a correctly rounded 1/x for the device's v_rcp_f32.  The
@@ -570,6 +581,7 @@ int rph_bvh_traversal_stats_ex(const rp_scene_desc* desc, const double* rays, ui
   rpb::BuildOptions bo;
   bo.node_format = node_format;
   bo.collapse = collapse == RP_COLLAPSE_GREEDY ? rpb::COLLAPSE_GREEDY : rpb::COLLAPSE_SAH;
+  always_options(always_max, always_minor, bo);
   rc = rpb::build(desc, bo, ps, err);
   if (rc != RP_OK) return fail(err);
   const bool q8 = ps.node_format != rpl::NODES_F32;  // Node4Q or Node8Q: the frame term
@@ -672,6 +684,14 @@ int rph_bvh_selfcheck(const rp_scene_desc* desc, uint32_t node_format, uint64_t*
 }
 
 int rph_bvh_selfcheck_ex(const rp_scene_desc* desc, uint32_t node_format, uint32_t collapse, uint64_t* stats) {
+  uint64_t st[6];
+  const int rc = rph_bvh_selfcheck_opt(desc, node_format, collapse, -1, 0, st);
+  if (rc == RP_OK && stats) std::memcpy(stats, st, 4 * sizeof(uint64_t));
+  return rc;
+}
+
+int rph_bvh_selfcheck_opt(const rp_scene_desc* desc, uint32_t node_format, uint32_t collapse, int32_t always_max,
+                          uint32_t always_minor, uint64_t* stats) {
   std::string err;
   int rc = rpb::validate(desc, err);
   if (rc != RP_OK) return fail(err);
@@ -679,6 +699,7 @@ int rph_bvh_selfcheck_ex(const rp_scene_desc* desc, uint32_t node_format, uint32
   rpb::BuildOptions bo;
   bo.node_format = node_format;
   bo.collapse = collapse == RP_COLLAPSE_GREEDY ? rpb::COLLAPSE_GREEDY : rpb::COLLAPSE_SAH;
+  always_options(always_max, always_minor, bo);
   rc = rpb::build(desc, bo, ps, err);
   if (rc != RP_OK) return fail(err);
   rc = rpb::check(ps, err);
@@ -691,11 +712,19 @@ int rph_bvh_selfcheck_ex(const rp_scene_desc* desc, uint32_t node_format, uint32
     stats[1] = ps.n_leaves;
     stats[2] = ps.max_depth;
     stats[3] = desc->n_hittables;
+    stats[4] = ps.n_always;
+    stats[5] = 0;  // non-triangle primitives inside the tree (the leaf-ordered records in front of the always tail)
+    for (uint32_t k = 0; k < ps.always_first; k++) stats[5] += ps.prims[k].kind != rpl::PRIM_TRIANGLE;
   }
   return RP_OK;
 }
 
 int rph_bvh_tree_hash(const rp_scene_desc* desc, uint32_t node_format, uint32_t threads, uint64_t* hash) {
+  return rph_bvh_tree_hash_opt(desc, node_format, threads, -1, 0, hash);
+}
+
+int rph_bvh_tree_hash_opt(const rp_scene_desc* desc, uint32_t node_format, uint32_t threads, int32_t always_max,
+                          uint32_t always_minor, uint64_t* hash) {
   std::string err;
   int rc = rpb::validate(desc, err);
   if (rc != RP_OK) return fail(err);
@@ -703,6 +732,7 @@ int rph_bvh_tree_hash(const rp_scene_desc* desc, uint32_t node_format, uint32_t 
   rpb::BuildOptions bo;
   bo.node_format = node_format;
   bo.threads = threads;
+  always_options(always_max, always_minor, bo);
   rc = rpb::build(desc, bo, ps, err);
   if (rc != RP_OK) return fail(err);
   uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a over the packed records

@@ -59,8 +59,12 @@ enum { DIAG_HIST = 64, DIAG_BIN_TICKS = RPK_DIAG_BIN_TICKS };
 enum {
   DREG_NODE, DREG_PRIM, DREG_STEP, DREG_SHADE, DREG_SURF, DREG_SPHUV, DREG_TEX, DREG_LAMBERT, DREG_METAL,
   DREG_DIELEC, DREG_LOOP_LAMBERT, DREG_LOOP_METAL, DREG_END_SAMPLE, DREG_END_PIXEL, DREG_START_SAMPLE,
-  DREG_REFILL, DREG_RNG_FALLBACK, DREG_JIT_FALLBACK, DREG_BEGIN_PIXEL, DREG_RING_LOAD, DREG_ROUND, DREG_MISS, DREG_N
+  DREG_REFILL, DREG_RNG_FALLBACK, DREG_JIT_FALLBACK, DREG_BEGIN_PIXEL, DREG_RING_LOAD, DREG_ROUND, DREG_MISS,
+  DREG_SPHERE_PATH,  // the sphere branch of a leaf iteration's prim_test (trav_step, trav_step_w8)
+  DREG_ALWAYS,       // one always-tested primitive's test (always_tests)
+  DREG_N             // at most 24: the regions end where the timeline histograms begin (DIAG_HIST)
 };
+static_assert(16 + 2 * DREG_N <= 64, "region counters run into the timeline histograms");
 
 // Division by a launch constant d >= 1 of numerators n < 2^31 (Granlund & Montgomery 1994, Thm 4.2 with N = 31):
 // l = ceil(log2 d), s = 31 + l, m = ceil(2^s / d) < 2^32 (m d - 2^s < d <= 2^l), and floor(n / d) = (n m) >> s.

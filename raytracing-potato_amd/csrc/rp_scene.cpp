@@ -158,6 +158,7 @@ int scene_create(const rp_scene_desc* desc, int device, const rp_scene_options* 
   bo.max_leaf = opt.max_leaf;
   bo.cost_traverse = opt.cost_traverse;
   bo.always_max = (uint32_t)opt.always_max;
+  bo.always_minor = true;  // a mesh scene's few spheres are tested once per ray, not in divergent leaves (rp_bvh.h)
   bo.collapse = opt.collapse == RP_COLLAPSE_GREEDY ? rpb::COLLAPSE_GREEDY : rpb::COLLAPSE_SAH;
   bo.node_format = opt.node_format;  // RP_NODES_AUTO (0) resolved by the builder
   phase[0] = lap();

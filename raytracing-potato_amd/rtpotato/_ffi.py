@@ -205,6 +205,7 @@ class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launc
 
 HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save", "rph_free", "rph_to_srgb_u8",
                 "rph_lookat", "rph_sky_panorama", "rph_bvh_selfcheck", "rph_bvh_traversal_stats", "rph_bvh_selfcheck_ex", "rph_bvh_traversal_stats_ex", "rph_bvh_tree_hash", "rph_last_error",
+                "rph_bvh_selfcheck_opt", "rph_bvh_traversal_stats_opt", "rph_bvh_tree_hash_opt",
                 "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
                 "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
@@ -356,6 +357,10 @@ def host() -> ctypes.CDLL:
     lib.rph_bvh_selfcheck_ex.argtypes = [POINTER(rp_scene_desc), c_uint32, c_uint32, POINTER(c_uint64)]
     lib.rph_bvh_traversal_stats_ex.argtypes = [POINTER(rp_scene_desc), c_void_p, c_uint64, c_uint32, c_uint32, c_void_p]
     lib.rph_bvh_tree_hash.argtypes = [POINTER(rp_scene_desc), c_uint32, c_uint32, POINTER(c_uint64)]
+    lib.rph_bvh_selfcheck_opt.argtypes = [POINTER(rp_scene_desc), c_uint32, c_uint32, ctypes.c_int32, c_uint32, POINTER(c_uint64)]
+    lib.rph_bvh_traversal_stats_opt.argtypes = [POINTER(rp_scene_desc), c_void_p, c_uint64, c_uint32, c_uint32, ctypes.c_int32,
+                                                c_uint32, c_void_p]
+    lib.rph_bvh_tree_hash_opt.argtypes = [POINTER(rp_scene_desc), c_uint32, c_uint32, ctypes.c_int32, c_uint32, POINTER(c_uint64)]
     lib.rph_last_error.restype = c_char_p
     lib.rph_stdrng_u64.argtypes = [c_void_p, c_uint64, c_uint64, c_void_p]
     lib.rph_make_div32.argtypes = [c_uint32, POINTER(c_uint32), POINTER(c_uint32)]

@@ -93,11 +93,13 @@ def main():
                               "tail_frac": round((t1 - tq) / (t1 - t0), 4)}
     regions = ["node", "prim", "step", "shade", "surface", "sph_uv", "texture", "lambert", "metal", "dielectric",
                "loop_lambert", "loop_metal", "end_sample", "end_pixel", "start_sample", "refill", "rng_fallback",
-               "jit_fallback", "begin_pixel", "ring_load", "round", "miss"]
+               "jit_fallback", "begin_pixel", "ring_load", "round", "miss", "sphere_path", "always_site"]
     out["regions"] = {
         name: {"wave_execs_per_kray": round(1000 * d[16 + 2 * i] / st["rays"], 2),
                "lane_util": round(d[17 + 2 * i] / max(1, 64 * d[16 + 2 * i]), 3)}
         for i, name in enumerate(regions)}
+    # P: the share of the leaf loop's iterations (prim) that run the sphere path beside the triangle's
+    out["sphere_path_share_of_prim_execs"] = round(d[16 + 2 * regions.index("sphere_path")] / max(1, d[16 + 2 * 1]), 4)
     cyc = ["surface", "sph_uv", "tex_issue", "scatter", "tex_value", "emit_accum", "start_sample", "end_sample",
            "newray_always", "refill", "next_bounce", "node_loop", "prim_loop"]
     out["cycle_share"] = {name: round(d[320 + i] / tot, 4) for i, name in enumerate(cyc)}
