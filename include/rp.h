@@ -642,7 +642,7 @@ int rp_accum_error_device_ws(rp_scene* scene, rp_workspace* workspace, const rp_
  * several streams per pixel, which it refuses).  It leaves the workspace's learned state exactly as it found it: no tile
  * is measured, no unit duration stored, no plan or cost table read or written; rp_workspace_frame_info reports 0 after it.
  * It waits on a pending frame gather as a render does.  The tiles go out in list order, in the queue chunks and frame
- * order of a shard of n_listed tiles (raytracing-potato_amd/csrc/rp_tiles_plan.h).  n_listed = 0: the counters are
+ * order of a shard of n_listed tiles (raytracing-potato_amd/csrc/rp_schedule.h).  n_listed = 0: the counters are
  * zeroed, nothing is launched, RP_OK.  RP_EINVAL: a NULL camera, params, d_rgb, d_counters or (n_listed > 0) d_tiles; a
  * sharded or balanced params; spp = 0; samples_per_stream < spp; n_listed above the frame's tile count; n_frames outside
  * 1..RP_MAX_FRAMES; a bad frame_order; what rp_render_frames_device_ws refuses about params and the launch's size. */

@@ -209,7 +209,7 @@ int rph_accum_tiles_select(const rp_render_params* params, const rp_error_params
                            const double* mean, const double* var, const uint32_t* tiles_in, uint32_t n_in, uint32_t* over,
                            uint32_t* tiles_out, uint32_t* count);
 
-/* Test hooks: what rp_render_tiles_device_ws launches with (raytracing-potato_amd/csrc/rp_tiles_plan.h
+/* Test hooks: what rp_render_tiles_device_ws launches with (raytracing-potato_amd/csrc/rp_schedule.h
  * rps::plan_tiles_launch, the header librp.so's rp_tiles.hip calls), in the pattern of rph_plan_launch and rph_unit_walk
  * for a whole-frame params given field by field (shard 0 of 1, interleave).  rph_plan_tiles_launch fills the
  * rph_launch_plan of a launch over n_listed tiles (n_shard_tiles = n_listed; plan_block 1, gather_stride and block_words

@@ -18,7 +18,7 @@
 // rp_variance.hip); the four statistics are
 // reduced in the wave, then in the block through LDS, then one vector atomic per block and statistic -- integer sums and
 // an integer maximum, so the result does not depend on the order of arrival.  zero_stats_kernel clears them first.
-#include "rp_state.h"  // first: the HIP runtime defines the qualifiers the shared headers use
+#include "rp_pass.h"  // first: the HIP runtime defines the qualifiers the shared headers use
 
 #include "rp_accum.h"
 #include "rp_units.h"
@@ -143,11 +143,8 @@ __global__ void __launch_bounds__(ACC_BLOCK) accum_tiles_kernel(const TileArgs T
   }
 }
 
-// the fields slot_pixel reads, under KParams' names, and the pass's own
 struct ErrArgs {
-  uint32_t W, H, tw, th, shard, nshards, tiles_x;
-  uint64_t n_slots;
-  const uint32_t* tile_map;  // the balanced plan's deal order (NULL = interleave)
+  rpp::ShardView v;
   const double* mean;        // 3 per slot
   const double* var;         // 3 per slot
   double tol2, eps;
@@ -165,11 +162,11 @@ __global__ void __launch_bounds__(ERR_BLOCK) error_kernel(const ErrArgs A) {
   unsigned long long n_counted = 0, n_over = 0, n_nonfinite = 0, bits = 0;
   // a block walks the slots in steps of the grid (the same trip count for all its lanes: the ballots and the barrier
   // below are reached by every lane); the counts are the wave's, the same in all its lanes
-  for (uint64_t base = (uint64_t)blockIdx.x * ERR_BLOCK; base < A.n_slots; base += (uint64_t)gridDim.x * ERR_BLOCK) {
+  for (uint64_t base = (uint64_t)blockIdx.x * ERR_BLOCK; base < A.v.n_slots; base += (uint64_t)gridDim.x * ERR_BLOCK) {
     const uint64_t slot = base + threadIdx.x;
     bool counted = false, over = false, nonfinite = false;
     uint32_t pi, pj;
-    if (slot < A.n_slots && rpk::slot_pixel(A, slot, pi, pj)) {
+    if (slot < A.v.n_slots && rpk::slot_pixel(A.v, slot, pi, pj)) {
       const double e2 = error2(A.mean + 3 * slot, A.var + 3 * slot, A.eps);
       counted = true;
       over = e2 > A.tol2;
@@ -214,10 +211,42 @@ __global__ void __launch_bounds__(ERR_BLOCK) error_kernel(const ErrArgs A) {
   }
 }
 
-static bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
+// What both folds refuse about their frame counts and their buffers, and the kernel's arguments.  A frame of the call
+// holds n_in blocks of block_words words and the state (d_mean, d_m2, d_var) n_state such blocks: the plain fold is one
+// block of n_words in both, without a list; the tile fold n_listed and n_state_tiles blocks of tile_words, with d_tiles
+// naming the state block of each listed one.  n_in = 0 (an empty list): nothing is read or launched, so nothing can
+// alias.
+static int fold_args(uint64_t block_words, uint32_t n_in, uint32_t n_state, const uint32_t* d_tiles, uint32_t n_prior,
+                     uint32_t n_frames, const double* d_frames, uint64_t frame_stride, double* d_mean, double* d_m2,
+                     double* d_var, AccArgs& a) {
+  using rpp::overlaps;
+  const uint64_t in_words = n_in * block_words, state_words = n_state * block_words;
+  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
+  if (frame_stride < in_words)
+    return fail(RP_EINVAL, d_tiles ? "frame_stride is below n_listed * tile_words: the frames would overlap"
+                                   : "frame_stride is below n_words: the frames would overlap");
+  const uint64_t n = (uint64_t)n_prior + n_frames;
+  if (n > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames (n_prior + n_frames)");
+  if (d_var && n < 2) return fail(RP_EINVAL, "the variance needs at least two frames (n_prior + n_frames >= 2)");
+  if (n_in == 0) return RP_OK;
+  // byte counts: the words are below 2^40 here; a stride that wraps 64 bits is the caller's address space running out
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + in_words), out_bytes = 8 * state_words;
+  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
+    if (overlaps(o, out_bytes, d_frames, in_bytes) || overlaps(o, out_bytes, d_tiles, 4ull * n_in))
+      return fail(RP_EINVAL, d_tiles ? "d_mean, d_m2 and d_var must not alias the frames or the list"
+                                     : "d_mean, d_m2 and d_var must not alias the frames");
+  if (overlaps(d_mean, out_bytes, d_m2, out_bytes) || overlaps(d_var, out_bytes, d_mean, out_bytes) ||
+      overlaps(d_var, out_bytes, d_m2, out_bytes))
+    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
+  a.n_words = block_words, a.stride = frame_stride;
+  a.n_prior = n_prior, a.n_frames = n_frames;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(d_frames) | reinterpret_cast<uintptr_t>(d_mean) |
+                         reinterpret_cast<uintptr_t>(d_m2) | reinterpret_cast<uintptr_t>(d_var);
+  // the wide path: every block starts on an even word of 16-byte aligned buffers, in the frames and in the state (the
+  // plain fold's one block starts each frame: an even stride is enough)
+  a.vec = bits % 16 == 0 && frame_stride % 2 == 0 && (d_tiles == nullptr || block_words % 2 == 0);
+  a.frames = d_frames, a.mean = d_mean, a.m2 = d_m2, a.var = d_var;
+  return RP_OK;
 }
 
 }  // namespace rpa
@@ -228,28 +257,11 @@ int rp_accum_frames_device(uint64_t n_words, uint32_t n_prior, uint32_t n_frames
                            uint64_t frame_stride, double* d_mean, double* d_m2, double* d_var, void* stream) {
   if (!d_frames || !d_mean || !d_m2) return fail(RP_EINVAL, "d_frames, d_mean and d_m2 must be non-NULL");
   if (n_words == 0) return fail(RP_EINVAL, "n_words is zero");
-  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
-  if (frame_stride < n_words) return fail(RP_EINVAL, "frame_stride is below n_words: the frames would overlap");
-  const uint64_t n = (uint64_t)n_prior + n_frames;
-  if (n > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames (n_prior + n_frames)");
-  if (d_var && n < 2) return fail(RP_EINVAL, "the variance needs at least two frames (n_prior + n_frames >= 2)");
   const uint64_t lanes = (n_words + 1) / 2, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
   if (grid > 0x7fffffffu) return fail(RP_EINVAL, "n_words is above 2^40 - 512: more than 2^31 - 1 blocks");
-  // byte counts: n_words < 2^40 here; a stride that wraps 64 bits is the caller's address space running out
-  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_words;
-  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
-    if (rpa::overlaps(o, out_bytes, d_frames, in_bytes))
-      return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias the frames");
-  if (rpa::overlaps(d_mean, out_bytes, d_m2, out_bytes) || rpa::overlaps(d_var, out_bytes, d_mean, out_bytes) ||
-      rpa::overlaps(d_var, out_bytes, d_m2, out_bytes))
-    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
   rpa::AccArgs a;
-  a.n_words = n_words, a.stride = frame_stride;
-  a.n_prior = n_prior, a.n_frames = n_frames;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(d_frames) | reinterpret_cast<uintptr_t>(d_mean) |
-                         reinterpret_cast<uintptr_t>(d_m2) | reinterpret_cast<uintptr_t>(d_var);
-  a.vec = bits % 16 == 0 && frame_stride % 2 == 0;
-  a.frames = d_frames, a.mean = d_mean, a.m2 = d_m2, a.var = d_var;
+  const int rc = rpa::fold_args(n_words, 1, 1, nullptr, n_prior, n_frames, d_frames, frame_stride, d_mean, d_m2, d_var, a);
+  if (rc) return rc;
   hipLaunchKernelGGL(rpa::accum_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, a);
   RP_HIP(hipGetLastError());
   return RP_OK;
@@ -260,32 +272,15 @@ int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, co
                                  double* d_mean, double* d_m2, double* d_var, void* stream) {
   if (!d_frames || !d_mean || !d_m2) return fail(RP_EINVAL, "d_frames, d_mean and d_m2 must be non-NULL");
   if (tile_words == 0) return fail(RP_EINVAL, "tile_words is zero");
-  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
   if (n_listed > n_state_tiles) return fail(RP_EINVAL, "n_listed is above n_state_tiles");
   if (n_listed && !d_tiles) return fail(RP_EINVAL, "d_tiles must be non-NULL");
   if (tile_words > (1ull << 40) - 512 || (uint64_t)n_state_tiles * tile_words > (1ull << 40) - 512)
     return fail(RP_EINVAL, "the state is above 2^40 - 512 words (n_state_tiles * tile_words)");
-  const uint64_t n_words = (uint64_t)n_listed * tile_words, n_state = (uint64_t)n_state_tiles * tile_words;
-  if (frame_stride < n_words) return fail(RP_EINVAL, "frame_stride is below n_listed * tile_words: the frames would overlap");
-  const uint64_t n = (uint64_t)n_prior + n_frames;
-  if (n > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames (n_prior + n_frames)");
-  if (d_var && n < 2) return fail(RP_EINVAL, "the variance needs at least two frames (n_prior + n_frames >= 2)");
-  if (n_listed == 0) return RP_OK;  // nothing listed: nothing folded, nothing launched
-  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_state;
-  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
-    if (rpa::overlaps(o, out_bytes, d_frames, in_bytes) || rpa::overlaps(o, out_bytes, d_tiles, 4ull * n_listed))
-      return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias the frames or the list");
-  if (rpa::overlaps(d_mean, out_bytes, d_m2, out_bytes) || rpa::overlaps(d_var, out_bytes, d_mean, out_bytes) ||
-      rpa::overlaps(d_var, out_bytes, d_m2, out_bytes))
-    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
   rpa::TileArgs t;
-  t.A.n_words = tile_words, t.A.stride = frame_stride;
-  t.A.n_prior = n_prior, t.A.n_frames = n_frames;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(d_frames) | reinterpret_cast<uintptr_t>(d_mean) |
-                         reinterpret_cast<uintptr_t>(d_m2) | reinterpret_cast<uintptr_t>(d_var);
-  // the wide path: every block starts on an even word of 16-byte aligned buffers, in the frames and in the state
-  t.A.vec = bits % 16 == 0 && frame_stride % 2 == 0 && tile_words % 2 == 0;
-  t.A.frames = d_frames, t.A.mean = d_mean, t.A.m2 = d_m2, t.A.var = d_var;
+  const int rc = rpa::fold_args(tile_words, n_listed, n_state_tiles, d_tiles, n_prior, n_frames, d_frames, frame_stride,
+                                d_mean, d_m2, d_var, t.A);
+  if (rc) return rc;
+  if (n_listed == 0) return RP_OK;  // nothing listed: nothing folded, nothing launched
   t.tiles = d_tiles, t.n_listed = n_listed, t.n_state = n_state_tiles;
   t.lanes_per_tile = (tile_words + 1) / 2;
   const uint64_t lanes = t.lanes_per_tile * n_listed, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
@@ -305,21 +300,14 @@ int rp_accum_error_device_ws(rp_scene* s, rp_workspace* w, const rp_render_param
   if (!rpa::resolve(e, tol, eps))
     return fail(RP_EINVAL, "error params out of range (tol > 0; eps > 0 and finite)");
   Tiling t;
-  if ((rc = frame_tiling(p, t))) return rc;
-  // a balanced shard holds the tiles of the beauty shard rendered before it: the plan that render left in the workspace
-  if (t.balanced && !w->plan_matches(p, t))
-    return fail(RP_EINVAL, "no balanced plan for this frame in the workspace: render it first");
+  rpa::ErrArgs a;
+  if ((rc = rpp::shard_view(w, p, t, a.v))) return rc;
   DeviceGuard g(s->device);
   static_assert(RP_ERROR_STATS_LEN == rpa::STATS_LEN, "include/rp.h and rp_accum.h disagree");
   hipLaunchKernelGGL(rpa::zero_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
                      reinterpret_cast<unsigned long long*>(d_stats));
   RP_HIP(hipGetLastError());
   if (t.n_slots == 0) return RP_OK;
-  rpa::ErrArgs a;
-  a.W = p->width, a.H = p->height, a.tw = t.tw, a.th = t.th, a.shard = t.shard, a.nshards = t.shards;
-  a.tiles_x = t.tiles_x;
-  a.n_slots = t.n_slots;
-  a.tile_map = t.balanced ? w->d_plan.get() : nullptr;
   a.mean = d_shard_mean, a.var = d_shard_var;
   a.tol2 = tol * tol, a.eps = eps;
   a.stats = reinterpret_cast<unsigned long long*>(d_stats);

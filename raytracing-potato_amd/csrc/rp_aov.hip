@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "rp_device.h"
-#include "rp_state.h"
+#include "rp_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -166,27 +166,6 @@ static int launch_aov(const KScene& s, const KParams& p, double* normal, double*
 
 }  // namespace rpk
 
-namespace {
-
-// rp_render.cpp's unpack_host (rp_shard_unpack): a compact shard buffer scattered into a frame, tiles dealt by `map`
-// (a balanced plan's deal order) or the interleave (map NULL).
-void unpack_host(const rp_render_params* p, const Tiling& t, const uint32_t* map, const void* shard_buf, size_t elem,
-                 uint32_t channels, void* frame) {
-  const uint64_t tile_px = (uint64_t)t.tw * t.th;
-  const char* src = static_cast<const char*>(shard_buf);
-  char* dst = static_cast<char*>(frame);
-  for (uint32_t k = 0; k < t.n_shard_tiles; k++) {
-    const uint32_t dk = t.shard + k * t.shards, tile = map ? map[dk] : dk;
-    const uint32_t ox = (tile % t.tiles_x) * t.tw, oy = (tile / t.tiles_x) * t.th;
-    for (uint32_t lj = 0; lj < t.th && oy + lj < p->height; lj++)
-      for (uint32_t li = 0; li < t.tw && ox + li < p->width; li++)
-        std::memcpy(dst + ((uint64_t)(oy + lj) * p->width + ox + li) * channels * elem,
-                    src + (k * tile_px + (uint64_t)lj * t.tw + li) * channels * elem, channels * elem);
-  }
-}
-
-}  // namespace
-
 extern "C" {
 
 int rp_render_aov_device_ws(rp_scene* s, rp_workspace* w, const rp_camera* cam, const rp_render_params* p,
@@ -197,10 +176,8 @@ int rp_render_aov_device_ws(rp_scene* s, rp_workspace* w, const rp_camera* cam, 
   if (!cam) return fail(RP_EINVAL, "camera is NULL");
   if (!d_normal && !d_albedo && !d_depth && !d_fg) return fail(RP_EINVAL, "every output is NULL");
   Tiling t;
-  if ((rc = frame_tiling(p, t))) return rc;
-  // a balanced shard holds the tiles of the beauty shard rendered before it: the plan that render left in the workspace
-  if (t.balanced && !w->plan_matches(p, t))
-    return fail(RP_EINVAL, "no balanced plan for this frame in the workspace: render it first");
+  rpk::KParams kp{};
+  if ((rc = rpp::shard_view(w, p, t, kp))) return rc;
   DeviceGuard g(s->device);
   const hipStream_t st = (hipStream_t)stream;
   if (d_counters) RP_HIP(hipMemsetAsync(d_counters, 0, sizeof(uint64_t) * rpk::CTR_N, st));
@@ -213,18 +190,8 @@ int rp_render_aov_device_ws(rp_scene* s, rp_workspace* w, const rp_camera* cam, 
     if (d_fg) RP_HIP(hipMemsetAsync(d_fg, 0xff, sizeof(float) * t.n_slots, st));
     return RP_OK;
   }
-  rpk::KParams kp{};
-  std::memcpy(kp.orient, cam->orientation, sizeof kp.orient);
-  std::memcpy(kp.pos, cam->position, sizeof kp.pos);
-  kp.aspect = cam->aspect_ratio;
-  kp.tan_fov = std::tan(0.5 * cam->fov);  // render.rs:33, on the host as the render does
-  kp.focal = cam->focal_dist;
-  kp.lens = cam->lens_radius;
-  kp.seed = p->seed;
-  kp.W = p->width, kp.H = p->height, kp.spp = p->spp;
-  kp.tw = t.tw, kp.th = t.th, kp.shard = t.shard, kp.nshards = t.shards;
-  kp.tiles_x = t.tiles_x, kp.n_shard_tiles = t.n_shard_tiles, kp.n_slots = t.n_slots;
-  kp.tile_map = t.balanced ? w->d_plan.get() : nullptr;
+  rpp::set_camera(kp, cam);
+  kp.seed = p->seed, kp.spp = p->spp, kp.n_shard_tiles = t.n_shard_tiles;
   RP_LAUNCH("feature pass", rpk::launch_aov(s->ks, kp, d_normal, d_albedo, d_depth, d_fg, d_counters, stream));
   return RP_OK;
 }
@@ -241,35 +208,25 @@ int rp_render_aov(rp_scene* s, const rp_camera* cam, const rp_render_params* p, 
   std::vector<double> normal(out_normal ? 3 * n : 0), albedo(out_albedo ? 3 * n : 0), depth(out_depth ? n : 0);
   std::vector<float> fg(out_fg ? n : 0);
   uint64_t ctr[rpk::CTR_N] = {0};
-  float ms = 0.f;
-  {
-    Stream st;
-    DevBuf<double> d_normal, d_albedo, d_depth;
-    DevBuf<float> d_fg;
-    DevBuf<uint64_t> d_ctr;
-    Event e0, e1;
-    if (hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking) != hipSuccess) return fail(RP_EHIP, "stream");
-    if ((out_normal && !d_normal.alloc(3 * n)) || (out_albedo && !d_albedo.alloc(3 * n)) ||
-        (out_depth && !d_depth.alloc(n)) || (out_fg && !d_fg.alloc(n)) || !d_ctr.alloc(rpk::CTR_N))
-      return fail(RP_ENOMEM, "hipMalloc output");
-    if (hipEventCreate(e0.put()) != hipSuccess || hipEventCreate(e1.put()) != hipSuccess) return fail(RP_EHIP, "event");
-    (void)hipEventRecord(e0.get(), st.get());
-    if ((rc = rp_render_aov_device_ws(s, nullptr, cam, p, d_normal.get(), d_albedo.get(), d_depth.get(), d_fg.get(),
-                                      d_ctr.get(), st.get())))
-      return rc;
-    (void)hipEventRecord(e1.get(), st.get());
-    hipError_t e = hipStreamSynchronize(st.get());
-    if (e != hipSuccess) return fail(RP_EHIP, std::string("feature pass: ") + hipGetErrorString(e));
-    (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
-    if ((out_normal && hipMemcpy(normal.data(), d_normal.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (out_albedo && hipMemcpy(albedo.data(), d_albedo.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (out_depth && hipMemcpy(depth.data(), d_depth.get(), sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (out_fg && hipMemcpy(fg.data(), d_fg.get(), sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
-        hipMemcpy(ctr, d_ctr.get(), sizeof ctr, hipMemcpyDeviceToHost) != hipSuccess)
-      return fail(RP_EHIP, "copy back");
-  }
-  if (ctr[rpk::CTR_STATUS] & rpk::STATUS_STACK_OVERFLOW) return fail(RP_EINTERNAL, "traversal stack overflow");
-  if (ctr[rpk::CTR_STATUS]) return fail(RP_EINTERNAL, "the feature pass reported a status bit");
+  double seconds = 0.0;
+  DevBuf<double> d_normal, d_albedo, d_depth;
+  DevBuf<float> d_fg;
+  DevBuf<uint64_t> d_ctr;
+  if ((out_normal && !d_normal.alloc(3 * n)) || (out_albedo && !d_albedo.alloc(3 * n)) ||
+      (out_depth && !d_depth.alloc(n)) || (out_fg && !d_fg.alloc(n)) || !d_ctr.alloc(rpk::CTR_N))
+    return fail(RP_ENOMEM, "hipMalloc output");
+  if ((rc = rpp::sync_call(s->device, "feature pass", &seconds, [&](void* st) {
+         return rp_render_aov_device_ws(s, nullptr, cam, p, d_normal.get(), d_albedo.get(), d_depth.get(), d_fg.get(),
+                                        d_ctr.get(), st);
+       })))
+    return rc;
+  if ((out_normal && hipMemcpy(normal.data(), d_normal.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (out_albedo && hipMemcpy(albedo.data(), d_albedo.get(), sizeof(double) * 3 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (out_depth && hipMemcpy(depth.data(), d_depth.get(), sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (out_fg && hipMemcpy(fg.data(), d_fg.get(), sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+      hipMemcpy(ctr, d_ctr.get(), sizeof ctr, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(RP_EHIP, "copy back");
+  if ((rc = rpp::check_status(ctr, "feature pass"))) return rc;
   if (t.n_slots) {
     std::vector<uint32_t> map;
     if (t.balanced) {
@@ -277,17 +234,12 @@ int rp_render_aov(rp_scene* s, const rp_camera* cam, const rp_render_params* p, 
       if ((rc = rp_workspace_tile_map(s, nullptr, p, map.data(), t.n_tiles))) return rc;
     }
     const uint32_t* m = t.balanced ? map.data() : nullptr;
-    if (out_normal) unpack_host(p, t, m, normal.data(), sizeof(double), 3, out_normal);
-    if (out_albedo) unpack_host(p, t, m, albedo.data(), sizeof(double), 3, out_albedo);
-    if (out_depth) unpack_host(p, t, m, depth.data(), sizeof(double), 1, out_depth);
-    if (out_fg) unpack_host(p, t, m, fg.data(), sizeof(float), 1, out_fg);
+    if (out_normal) rpp::unpack_host(p, t, m, normal.data(), sizeof(double), 3, out_normal);
+    if (out_albedo) rpp::unpack_host(p, t, m, albedo.data(), sizeof(double), 3, out_albedo);
+    if (out_depth) rpp::unpack_host(p, t, m, depth.data(), sizeof(double), 1, out_depth);
+    if (out_fg) rpp::unpack_host(p, t, m, fg.data(), sizeof(float), 1, out_fg);
   }
-  if (stats) {
-    stats->rays = ctr[rpk::CTR_RAYS];
-    stats->samples = ctr[rpk::CTR_SAMPLES];
-    stats->pixels = ctr[rpk::CTR_PIXELS];
-    stats->seconds = ms * 1e-3;
-  }
+  rpp::fill_stats(ctr, seconds, stats);
   return RP_OK;
 }
 

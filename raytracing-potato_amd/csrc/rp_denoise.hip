@@ -19,7 +19,7 @@
 // The variance-guided filter (rp_denoise_var*) is the instantiation VAR = true of the same kernel: the
 // pixel record grows from 11 to 12 doubles by the variance v (made from var and the albedo as the first level loads,
 // ping-ponged in scratch beside the colour after it), and the 3 x 3 prefilter of v reads taps the tile already holds.
-#include "rp_hip_util.h"  // first: the HIP runtime defines the qualifiers rp_denoise.h uses
+#include "rp_pass.h"  // first: the HIP runtime defines the qualifiers rp_denoise.h uses
 
 #include "rp_denoise.h"
 
@@ -127,11 +127,10 @@ namespace {
 
 constexpr uint32_t DIM_MAX = 65535;  // a frame's width and height, as the renders' (rp_schedule.h make_tiling)
 
-bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
+using rpp::overlaps;
+
+// Doubles of scratch per pixel: two colour buffers (3 each) and, with the variance, two variance buffers (1 each).
+constexpr uint64_t scratch_doubles(bool var) { return var ? 2 * (3 + 1) : 2 * 3; }
 
 int check_frame(uint32_t width, uint32_t height) {
   if (width == 0 || height == 0) return fail(RP_EINVAL, "width and height must be >= 1");
@@ -141,9 +140,9 @@ int check_frame(uint32_t width, uint32_t height) {
 
 // What rp_denoise_device and rp_denoise_var_device refuse about their buffers (d_var NULL: the former).
 int check_buffers(uint32_t width, uint32_t height, const double* d_rgb, const double* d_var, const double* d_normal,
-                  const double* d_albedo, const double* d_depth, const double* d_out, const void* d_scratch,
-                  uint64_t scratch_bytes) {
+                  const double* d_albedo, const double* d_depth, const double* d_out, const void* d_scratch) {
   const uint64_t n = (uint64_t)width * height, b3 = 3 * n * sizeof(double), b1 = n * sizeof(double);
+  const uint64_t scratch_bytes = scratch_doubles(d_var != nullptr) * b1;
   if (overlaps(d_out, b3, d_rgb, b3) || overlaps(d_out, b3, d_normal, b3) || overlaps(d_out, b3, d_albedo, b3) ||
       overlaps(d_out, b3, d_depth, b1) || overlaps(d_out, b3, d_var, b3))
     return fail(RP_EINVAL, "out must not alias an input");
@@ -189,8 +188,8 @@ int launch_levels(const Params& P, uint32_t iterations, uint32_t width, uint32_t
   return RP_OK;
 }
 
-// rp_denoise and rp_denoise_var: the frames up, `enqueue(buffers..., stream)` timed by events, the result down.
-// var NULL: rp_denoise (scratch of 6 doubles per pixel instead of 8).
+// rp_denoise and rp_denoise_var: the frames up, `enqueue(buffers..., stream)` as a synchronous call, the result down.
+// var NULL: rp_denoise.
 template <class Enqueue>
 int denoise_sync(int device, uint32_t width, uint32_t height, const double* rgb, const double* var, const double* normal,
                  const double* albedo, const double* depth, double* out, double* seconds, Enqueue enqueue) {
@@ -202,33 +201,23 @@ int denoise_sync(int device, uint32_t width, uint32_t height, const double* rgb,
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RP_ENODEV, "no HIP device");
   if (device < 0 || device >= count) return fail(RP_EINVAL, "device out of range");
   DeviceGuard g(device);
-  float ms = 0.f;
-  {
-    Stream st;
-    Event e0, e1;
-    DevBuf<double> d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch;
-    if (hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking) != hipSuccess) return fail(RP_EHIP, "stream");
-    if (!d_rgb.alloc(3 * n) || !d_out.alloc(3 * n) || !d_scratch.alloc(var ? 8 * n : 6 * n) ||
-        (var && !d_var.alloc(3 * n)) || (normal && !d_normal.alloc(3 * n)) || (albedo && !d_albedo.alloc(3 * n)) ||
-        (depth && !d_depth.alloc(n)))
-      return fail(RP_ENOMEM, "hipMalloc frame buffers");
-    if (hipEventCreate(e0.put()) != hipSuccess || hipEventCreate(e1.put()) != hipSuccess) return fail(RP_EHIP, "event");
-    RP_HIP(hipMemcpy(d_rgb.get(), rgb, 24 * n, hipMemcpyHostToDevice));
-    if (var) RP_HIP(hipMemcpy(d_var.get(), var, 24 * n, hipMemcpyHostToDevice));
-    if (normal) RP_HIP(hipMemcpy(d_normal.get(), normal, 24 * n, hipMemcpyHostToDevice));
-    if (albedo) RP_HIP(hipMemcpy(d_albedo.get(), albedo, 24 * n, hipMemcpyHostToDevice));
-    if (depth) RP_HIP(hipMemcpy(d_depth.get(), depth, 8 * n, hipMemcpyHostToDevice));
-    (void)hipEventRecord(e0.get(), st.get());
-    const int rc = enqueue(d_rgb.get(), d_var.get(), d_normal.get(), d_albedo.get(), d_depth.get(), d_out.get(),
-                           d_scratch.get(), st.get());
-    if (rc) return rc;
-    (void)hipEventRecord(e1.get(), st.get());
-    const hipError_t e = hipStreamSynchronize(st.get());
-    if (e != hipSuccess) return fail(RP_EHIP, std::string("denoise: ") + hipGetErrorString(e));
-    (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
-    RP_HIP(hipMemcpy(out, d_out.get(), 24 * n, hipMemcpyDeviceToHost));
-  }
-  if (seconds) *seconds = ms * 1e-3;
+  DevBuf<double> d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch;
+  if (!d_rgb.alloc(3 * n) || !d_out.alloc(3 * n) || !d_scratch.alloc(scratch_doubles(var != nullptr) * n) ||
+      (var && !d_var.alloc(3 * n)) || (normal && !d_normal.alloc(3 * n)) || (albedo && !d_albedo.alloc(3 * n)) ||
+      (depth && !d_depth.alloc(n)))
+    return fail(RP_ENOMEM, "hipMalloc frame buffers");
+  RP_HIP(hipMemcpy(d_rgb.get(), rgb, 24 * n, hipMemcpyHostToDevice));
+  if (var) RP_HIP(hipMemcpy(d_var.get(), var, 24 * n, hipMemcpyHostToDevice));
+  if (normal) RP_HIP(hipMemcpy(d_normal.get(), normal, 24 * n, hipMemcpyHostToDevice));
+  if (albedo) RP_HIP(hipMemcpy(d_albedo.get(), albedo, 24 * n, hipMemcpyHostToDevice));
+  if (depth) RP_HIP(hipMemcpy(d_depth.get(), depth, 8 * n, hipMemcpyHostToDevice));
+  double s = 0.0;
+  const int rc = rpp::sync_call(device, "denoise", &s, [&](void* st) {
+    return enqueue(d_rgb.get(), d_var.get(), d_normal.get(), d_albedo.get(), d_depth.get(), d_out.get(), d_scratch.get(), st);
+  });
+  if (rc) return rc;
+  RP_HIP(hipMemcpy(out, d_out.get(), 24 * n, hipMemcpyDeviceToHost));
+  if (seconds) *seconds = s;
   return RP_OK;
 }
 
@@ -249,7 +238,7 @@ int rp_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
   int rc = check_frame(width, height);
   if (rc) return rc;
   if (!bytes) return fail(RP_EINVAL, "bytes is NULL");
-  *bytes = 2ull * 3ull * sizeof(double) * width * height;  // two colour buffers
+  *bytes = scratch_doubles(false) * sizeof(double) * width * height;
   return RP_OK;
 }
 
@@ -263,9 +252,7 @@ int rp_denoise_device(const rp_denoise_params* params, uint32_t width, uint32_t 
   if (!rpdn::resolve(params, P))
     return fail(RP_EINVAL, "denoise params out of range: iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo "
                            "and albedo_eps > 0 and finite, sigma_color finite (negative disables)");
-  if ((rc = check_buffers(width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out, d_scratch,
-                          2ull * 24 * width * height)))
-    return rc;
+  if ((rc = check_buffers(width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out, d_scratch))) return rc;
   return launch_levels<false>(P, P.iterations, width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out,
                               d_scratch, stream);
 }
@@ -294,7 +281,7 @@ int rp_denoise_var_scratch_bytes(uint32_t width, uint32_t height, uint64_t* byte
   int rc = check_frame(width, height);
   if (rc) return rc;
   if (!bytes) return fail(RP_EINVAL, "bytes is NULL");
-  *bytes = 2ull * (3ull + 1ull) * sizeof(double) * width * height;  // two colour and two variance buffers
+  *bytes = scratch_doubles(true) * sizeof(double) * width * height;
   return RP_OK;
 }
 
@@ -306,9 +293,7 @@ int rp_denoise_var_device(const rp_denoise_var_params* params, uint32_t width, u
   if (!d_rgb || !d_var || !d_out || !d_scratch) return fail(RP_EINVAL, "rgb, var, out and scratch must be non-NULL");
   rp_denoise_var_params P;
   if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, VAR_RANGE);
-  if ((rc = check_buffers(width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch,
-                          2ull * 32 * width * height)))
-    return rc;
+  if ((rc = check_buffers(width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch))) return rc;
   return launch_levels<true>(P, P.base.iterations, width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out,
                              d_scratch, stream);
 }

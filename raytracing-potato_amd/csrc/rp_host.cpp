@@ -21,7 +21,6 @@
 #include "rp_kernel.h"
 #include "rp_ray.h"
 #include "rp_schedule.h"
-#include "rp_tiles_plan.h"
 #include "rp_units.h"
 
 namespace {
@@ -1288,7 +1287,7 @@ int rph_accum_tiles_select(const rp_render_params* params, const rp_error_params
   return RP_OK;
 }
 
-// The plan of a tile-list launch (rp_tiles_plan.h rps::plan_tiles_launch, what rp_render_tiles_device_ws launches with).
+// The plan of a tile-list launch (rp_schedule.h rps::plan_tiles_launch, what rp_render_tiles_device_ws launches with).
 static rps::Refusal tiles_plan(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_bounce, uint32_t tile_w,
                                uint32_t tile_h, uint32_t samples_per_stream, uint32_t n_listed, uint32_t n_frames,
                                uint32_t frame_order, uint32_t unit_queues, uint32_t queue_chunk, uint64_t lanes,

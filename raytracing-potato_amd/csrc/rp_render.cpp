@@ -1,9 +1,7 @@
 // rp_render.cpp -- the render side of the C-ABI in include/rp.h (librp.so): the workspace, the stages of a shard's
 // render (render_shard: plan, tile costs, balanced deal, tile and unit order, the persistent kernel's launch, batch
 // reduce, learned costs) and the calls that read a workspace's scheduling state back.
-#include <cmath>
-
-#include "rp_state.h"
+#include "rp_pass.h"
 
 // Allocate a workspace for scene s (current device = the scene's): counters, queues, probe/sort buffers
 // and a keystream slab for every lane the render grid can hold resident.
@@ -75,23 +73,6 @@ int ws_reserve(rp_scene* s, rp_workspace* w, const rp_render_params* p, bool gat
 
 namespace {
 
-// Scatter a compact shard buffer into a frame on the host (rp_shard_unpack), tiles dealt by `map` (the deal order
-// of a balanced plan) or the interleave (map NULL).
-void unpack_host(const rp_render_params* p, const Tiling& t, const uint32_t* map, const void* shard_buf, size_t elem,
-                 uint32_t channels, void* frame) {
-  const uint64_t tile_px = (uint64_t)t.tw * t.th;
-  const char* src = static_cast<const char*>(shard_buf);
-  char* dst = static_cast<char*>(frame);
-  for (uint32_t k = 0; k < t.n_shard_tiles; k++) {
-    const uint32_t dk = t.shard + k * t.shards, tile = map ? map[dk] : dk;
-    const uint32_t ox = (tile % t.tiles_x) * t.tw, oy = (tile / t.tiles_x) * t.th;
-    for (uint32_t lj = 0; lj < t.th && oy + lj < p->height; lj++)
-      for (uint32_t li = 0; li < t.tw && ox + li < p->width; li++)
-        std::memcpy(dst + ((uint64_t)(oy + lj) * p->width + ox + li) * channels * elem,
-                    src + (k * tile_px + (uint64_t)lj * t.tw + li) * channels * elem, channels * elem);
-  }
-}
-
 // One render_shard call: what its stages share.  Every stage enqueues on `stream`, in the order render_shard calls them.
 struct Launch {
   rp_scene* s;
@@ -112,17 +93,6 @@ struct Launch {
   hipStream_t st() const { return (hipStream_t)stream; }
   int grid_for(uint64_t units) const { return rps::grid_for(units, s->resident()); }
 };
-
-int wait_and_clear(Launch& L) {
-  rp_workspace* w = L.w;
-  // the last frame gather on this workspace (another stream, perhaps) has read d_meas and written d_fcost
-  if (w->gathered_pending) {
-    RP_HIP(hipStreamWaitEvent(L.st(), w->ev_gathered.get(), 0));
-    w->gathered_pending = false;
-  }
-  RP_HIP(hipMemsetAsync(L.ctr, 0, sizeof(uint64_t) * rpk::CTR_N, L.st()));
-  return RP_OK;
-}
 
 // The cost probe: sample 0 of an n x n lattice of pixels per tile traced by the probe instantiation of the
 // render kernel, which adds up per tile the traversal work and shaded rays (summed and costliest sample) --
@@ -301,7 +271,7 @@ int render_shard(rp_scene* s, rp_workspace* w, const rp_camera* cam, const rp_re
   const Tiling& t = L.lp.t;
   rpk::KParams& kp = L.lp.kp;
   DeviceGuard g(s->device);
-  int rc = wait_and_clear(L);
+  int rc = rpp::launch_begin(w, L.ctr, L.st());
   if (rc) return rc;
   if (t.n_slots == 0) return RP_OK;
   if (p->spp == 0) {
@@ -312,12 +282,7 @@ int render_shard(rp_scene* s, rp_workspace* w, const rp_camera* cam, const rp_re
   }
   refused = rps::launch_limits(L.lp, s->lanes());
   if (refused.code) return fail(refused.code, refused.msg);
-  std::memcpy(kp.orient, cam->orientation, sizeof kp.orient);
-  std::memcpy(kp.pos, cam->position, sizeof kp.pos);
-  kp.aspect = cam->aspect_ratio;
-  kp.tan_fov = std::tan(0.5 * cam->fov);  // render.rs:33, hoisted: a per-camera constant
-  kp.focal = cam->focal_dist;
-  kp.lens = cam->lens_radius;
+  rpp::set_camera(kp, cam);
   if (kp.nbatch > 1) {
     if (kp.n_queue > w->d_partial_hits.capacity() || 3 * kp.n_queue > w->d_partial.capacity())
       return fail(RP_EINVAL, n_frames > 1 ? "workspace not reserved for these frames' sample batches: call "
@@ -326,13 +291,9 @@ int render_shard(rp_scene* s, rp_workspace* w, const rp_camera* cam, const rp_re
     kp.partial = w->d_partial.get();
     kp.partial_hits = w->d_partial_hits.get();
   }
-  L.ks = s->ks;
-  L.ks.rng_slab = reinterpret_cast<uint32_t*>(w->d_slab.get());
-  L.ks.spill = w->d_spill.get();
-  L.ks.unit_t0 = w->d_t0.get();
-  RP_HIP(hipMemsetAsync(w->d_queue.get(), 0, sizeof(uint32_t) * rpk::QUEUE_WORDS, L.st()));
-  if ((rc = tile_costs(L)) || (rc = balanced_plan(L)) || (rc = tile_order(L)) || (rc = unit_order(L)) ||
-      (rc = launch_units(L)) || (rc = reduce_batches(L)) || (rc = learn_costs(L)))
+  if ((rc = rpp::launch_bind(s, w, L.ks, L.st())) || (rc = tile_costs(L)) || (rc = balanced_plan(L)) ||
+      (rc = tile_order(L)) || (rc = unit_order(L)) || (rc = launch_units(L)) || (rc = reduce_batches(L)) ||
+      (rc = learn_costs(L)))
     return rc;
   return RP_OK;
 }
@@ -366,7 +327,7 @@ int rp_shard_unpack(const rp_render_params* p, const double* shard_buf, uint32_t
   if (rc) return rc;
   if (!shard_buf || !frame || channels == 0) return fail(RP_EINVAL, "NULL buffer or zero channels");
   if (t.balanced) return fail(RP_EINVAL, "balanced frame: unpack with rp_shard_unpack_map and rp_workspace_tile_map");
-  unpack_host(p, t, nullptr, shard_buf, sizeof(double), channels, frame);
+  rpp::unpack_host(p, t, nullptr, shard_buf, sizeof(double), channels, frame);
   return RP_OK;
 }
 
@@ -383,7 +344,7 @@ int rp_shard_unpack_map(const rp_render_params* p, const uint32_t* tile_map, con
       seen[tile_map[i]] = 1;
     }
   }
-  unpack_host(p, t, tile_map, shard_buf, sizeof(double), channels, frame);
+  rpp::unpack_host(p, t, tile_map, shard_buf, sizeof(double), channels, frame);
   return RP_OK;
 }
 
@@ -518,44 +479,31 @@ int rp_render(rp_scene* s, const rp_camera* cam, const rp_render_params* p, doub
   std::vector<double> shard(3 * (t.n_slots ? t.n_slots : 1));
   std::vector<float> shard_fg(out_fg ? (t.n_slots ? t.n_slots : 1) : 0);
   uint64_t ctr[rpk::CTR_N] = {0};
-  float ms = 0.f;
-  {
-    Stream st;
-    DevBuf<double> d_rgb;
-    DevBuf<float> d_fg;
-    DevBuf<uint64_t> d_ctr;
-    Event e0, e1;
-    if (hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking) != hipSuccess) return fail(RP_EHIP, "stream");
-    if (!d_rgb.alloc(shard.size()) || !d_ctr.alloc(rpk::CTR_N) || (out_fg && !d_fg.alloc(shard_fg.size())))
-      return fail(RP_ENOMEM, "hipMalloc output");
-    if (hipEventCreate(e0.put()) != hipSuccess || hipEventCreate(e1.put()) != hipSuccess) return fail(RP_EHIP, "event");
-    (void)hipEventRecord(e0.get(), st.get());
-    if ((rc = render_shard(s, &s->ws0, cam, p, d_rgb.get(), d_fg.get(), d_ctr.get(), st.get()))) return rc;
-    (void)hipEventRecord(e1.get(), st.get());
-    hipError_t e = hipStreamSynchronize(st.get());
-    if (e != hipSuccess) return fail(RP_EHIP, std::string("render: ") + hipGetErrorString(e));
-    (void)hipEventElapsedTime(&ms, e0.get(), e1.get());
-    if (hipMemcpy(shard.data(), d_rgb.get(), sizeof(double) * shard.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(ctr, d_ctr.get(), sizeof ctr, hipMemcpyDeviceToHost) != hipSuccess ||
-        (out_fg && hipMemcpy(shard_fg.data(), d_fg.get(), sizeof(float) * shard_fg.size(), hipMemcpyDeviceToHost) != hipSuccess))
-      return fail(RP_EHIP, "copy back");
-  }
-  if (ctr[rpk::CTR_STATUS] & rpk::STATUS_STACK_OVERFLOW) return fail(RP_EINTERNAL, "traversal stack overflow");
+  double seconds = 0.0;
+  DevBuf<double> d_rgb;
+  DevBuf<float> d_fg;
+  DevBuf<uint64_t> d_ctr;
+  if (!d_rgb.alloc(shard.size()) || !d_ctr.alloc(rpk::CTR_N) || (out_fg && !d_fg.alloc(shard_fg.size())))
+    return fail(RP_ENOMEM, "hipMalloc output");
+  if ((rc = rpp::sync_call(s->device, "render", &seconds, [&](void* st) {
+         return render_shard(s, &s->ws0, cam, p, d_rgb.get(), d_fg.get(), d_ctr.get(), st);
+       })))
+    return rc;
+  if (hipMemcpy(shard.data(), d_rgb.get(), sizeof(double) * shard.size(), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(ctr, d_ctr.get(), sizeof ctr, hipMemcpyDeviceToHost) != hipSuccess ||
+      (out_fg && hipMemcpy(shard_fg.data(), d_fg.get(), sizeof(float) * shard_fg.size(), hipMemcpyDeviceToHost) != hipSuccess))
+    return fail(RP_EHIP, "copy back");
+  if ((rc = rpp::check_status(ctr, nullptr))) return rc;
   if (t.n_slots) {
     std::vector<uint32_t> map;
     if (t.balanced) {
       map.resize(t.n_tiles);
       if ((rc = rp_workspace_tile_map(s, &s->ws0, p, map.data(), t.n_tiles))) return rc;
     }
-    unpack_host(p, t, t.balanced ? map.data() : nullptr, shard.data(), sizeof(double), 3, out_rgb);
-    if (out_fg) unpack_host(p, t, t.balanced ? map.data() : nullptr, shard_fg.data(), sizeof(float), 1, out_fg);
+    rpp::unpack_host(p, t, t.balanced ? map.data() : nullptr, shard.data(), sizeof(double), 3, out_rgb);
+    if (out_fg) rpp::unpack_host(p, t, t.balanced ? map.data() : nullptr, shard_fg.data(), sizeof(float), 1, out_fg);
   }
-  if (stats) {
-    stats->rays = ctr[rpk::CTR_RAYS];
-    stats->samples = ctr[rpk::CTR_SAMPLES];
-    stats->pixels = ctr[rpk::CTR_PIXELS];
-    stats->seconds = ms * 1e-3;
-  }
+  rpp::fill_stats(ctr, seconds, stats);
   return RP_OK;
 }
 

@@ -98,6 +98,10 @@ inline uint64_t pack_words(const Tiling& t, bool bgra, uint32_t n_frames = 1) {
 
 constexpr uint32_t DEF_UNIT_QUEUES = RP_QUEUES_XCD_TILES;
 constexpr uint32_t QUEUE_CHUNK_AUTO = 8;  // rp_scene_options.queue_chunk = 0: tiles per queue chunk (plan_launch)
+// The queue mode in effect (rp.h RP_QUEUES_*): AUTO resolved.
+inline uint32_t queue_mode(const rp_scene_options& opt) {
+  return opt.unit_queues == RP_QUEUES_AUTO ? DEF_UNIT_QUEUES : opt.unit_queues;
+}
 
 // What a render of n_frames frames of params' shard is launched with: the scalar fields of its kernel parameters (the
 // camera and every device pointer are the caller's to fill) and the scheduling stages it takes.
@@ -118,9 +122,11 @@ inline int grid_for(uint64_t units, uint64_t resident) {
   return (int)std::max<uint64_t>(1, std::min(want, resident));
 }
 
-// opt: the scene's resolved options (unit_queues, queue_chunk, trav_threshold).
-inline Refusal plan_launch(const rp_render_params* p, uint32_t n_frames, uint32_t frame_order,
-                           const rp_scene_options& opt, LaunchPlan& out) {
+// A launch is planned in two steps.  The first: the checks, the tiling and every field that depends on the frame, its
+// tiles' size and the launch's frame count alone.  opt: the scene's resolved options (unit_queues, queue_chunk,
+// trav_threshold).
+inline Refusal plan_frame(const rp_render_params* p, uint32_t n_frames, uint32_t frame_order, const rp_scene_options& opt,
+                          LaunchPlan& out) {
   if (n_frames == 0 || n_frames > RP_MAX_FRAMES) return {RP_EINVAL, "n_frames must be 1..RP_MAX_FRAMES"};
   if (frame_order > RP_FRAME_ORDER_PIXEL) return {RP_EINVAL, "frame_order must be an RP_FRAME_ORDER_* value"};
   Tiling& t = out.t;
@@ -132,44 +138,85 @@ inline Refusal plan_launch(const rp_render_params* p, uint32_t n_frames, uint32_
   kp.seed = p->seed;
   kp.W = p->width, kp.H = p->height, kp.spp = p->spp, kp.max_bounce = p->max_bounce;
   kp.tw = t.tw, kp.th = t.th, kp.shard = t.shard, kp.nshards = t.shards;
-  kp.tiles_x = t.tiles_x, kp.n_shard_tiles = t.n_shard_tiles, kp.n_slots = t.n_slots;
+  kp.tiles_x = t.tiles_x;
   kp.trav_threshold = opt.trav_threshold;
   kp.spp_batch = t.sps;  // the RNG contract's samples per stream (rp_render_params.samples_per_stream)
   kp.nbatch = t.nbatch;
-  kp.n_queue = t.n_slots * kp.nbatch * n_frames;  // every frame's units
   kp.n_frames = n_frames;
-  kp.dv_tiles = rpk::make_div32(std::max(1u, t.n_shard_tiles));
   kp.dv_frames = rpk::make_div32(n_frames);
-  kp.frames_inter = n_frames > 1 && frame_order != RP_FRAME_ORDER_SEQUENTIAL ? 1u : 0u;
-  kp.out_stride = 3 * t.n_slots;
   // Per-XCD queues (rp.h RP_QUEUES_*): groups of blocks blockIdx mod 8 share an XCD (MI355X_MICROARCH.md,
   // observed round-robin dispatch; speed only -- any placement gives the same image).
-  const uint32_t qmode = opt.unit_queues == RP_QUEUES_AUTO ? DEF_UNIT_QUEUES : opt.unit_queues;
-  kp.queue_groups = qmode == RP_QUEUES_SINGLE ? 1u : (uint32_t)rpk::QUEUE_GROUPS;
+  kp.queue_groups = queue_mode(opt) == RP_QUEUES_SINGLE ? 1u : (uint32_t)rpk::QUEUE_GROUPS;
+  kp.dv_units = rpk::make_div32(std::max(1u, t.tw * t.th * kp.nbatch));
+  kp.dv_nbatch = rpk::make_div32(kp.nbatch ? kp.nbatch : 1u);
+  kp.dv_tiles_x = rpk::make_div32(t.tiles_x);
+  kp.dv_tw = rpk::make_div32(t.tw);
+  return {};
+}
+
+// The second: the launch runs n_shard_tiles tiles -- the shard's, or a caller's list -- and everything that depends on
+// their count: the slots, the queue entries, the frames' stride, the queue chunk and the frame order that depends on it.
+inline void plan_tiles(uint32_t n_shard_tiles, uint32_t n_frames, uint32_t frame_order, const rp_scene_options& opt,
+                       LaunchPlan& out) {
+  Tiling& t = out.t;
+  rpk::KParams& kp = out.kp;
+  t.n_shard_tiles = n_shard_tiles;
+  t.n_slots = (uint64_t)n_shard_tiles * t.tw * t.th;
+  kp.n_shard_tiles = n_shard_tiles, kp.n_slots = t.n_slots;
+  kp.n_queue = t.n_slots * kp.nbatch * n_frames;  // every frame's units
+  kp.dv_tiles = rpk::make_div32(std::max(1u, n_shard_tiles));
+  kp.frames_inter = n_frames > 1 && frame_order != RP_FRAME_ORDER_SEQUENTIAL ? 1u : 0u;
+  kp.out_stride = 3 * t.n_slots;
   // Default chunk: up to 8 consecutive (virtual) tiles of the order per queue at a time, while every queue still gets >= 16
   // chunks -- the tiles one XCD runs together are then neighbours in cost and, inside a cost bucket, in Z-order (a whole C3
   // frame, 2,040 tiles: chunks of 8, -1.0 % against chunks of one; an 8-way shard, 255 tiles: chunks of one, 8 cost
   // +3.8 % at one frame per launch); with interleaved frames a whole number of tiles of every frame (n_frames >= 8: one
   // tile of every frame, so one XCD renders a tile for all the launch's frames and its L2 serves the same pixels' rays
   // n_frames times: C3 -1.3 %, 8-way shards -1.9 %)
-  const uint64_t vtiles = (uint64_t)t.n_shard_tiles * n_frames;
+  const uint64_t vtiles = (uint64_t)n_shard_tiles * n_frames;
   uint32_t chunk_auto = 1;
   while (chunk_auto < QUEUE_CHUNK_AUTO && 2ull * chunk_auto * 8 * 16 <= vtiles) chunk_auto *= 2;
   if (kp.frames_inter) chunk_auto = n_frames * ((chunk_auto + n_frames - 1) / n_frames);
-  kp.queue_chunk = qmode == RP_QUEUES_XCD_REGIONS ? (t.n_shard_tiles + kp.queue_groups - 1) / kp.queue_groups
+  kp.queue_chunk = queue_mode(opt) == RP_QUEUES_XCD_REGIONS ? (n_shard_tiles + kp.queue_groups - 1) / kp.queue_groups
                   : kp.queue_groups > 1 ? (opt.queue_chunk ? opt.queue_chunk : chunk_auto) : 1u;
   if (kp.queue_chunk == 0) kp.queue_chunk = 1;
   // RP_FRAME_ORDER_PIXEL needs a queue's runs of n_frames virtual tiles to be one tile of every frame: single queue, or
   // chunks of whole multiples of n_frames (the default chunk is); otherwise it is INTERLEAVED
   if (kp.frames_inter && frame_order == RP_FRAME_ORDER_PIXEL && (kp.queue_groups == 1 || kp.queue_chunk % n_frames == 0))
     kp.frames_inter = 2;
-  kp.dv_units = rpk::make_div32(std::max(1u, t.tw * t.th * kp.nbatch));
-  kp.dv_nbatch = rpk::make_div32(kp.nbatch ? kp.nbatch : 1u);
-  kp.dv_tiles_x = rpk::make_div32(t.tiles_x);
-  kp.dv_tw = rpk::make_div32(t.tw);
   kp.dv_chunk = rpk::make_div32(kp.queue_chunk);
+}
+
+// A render of n_frames frames of params' shard (render_shard).
+inline Refusal plan_launch(const rp_render_params* p, uint32_t n_frames, uint32_t frame_order,
+                           const rp_scene_options& opt, LaunchPlan& out) {
+  const Refusal r = plan_frame(p, n_frames, frame_order, opt, out);
+  if (r.code) return r;
+  const Tiling& t = out.t;
+  plan_tiles(t.n_shard_tiles, n_frames, frame_order, opt, out);
   out.sortable = t.n_shard_tiles > 1 && t.n_shard_tiles <= rpk::TILE_SORT_MAX && t.tiles_x <= 256 && t.tiles_y <= 256;
   out.measure = t.n_shard_tiles <= (uint32_t)rpk::TILE_SORT_MAX;
+  return {};
+}
+
+// A render over a caller-given list of n_listed frame tiles (include/rp.h rp_render_tiles_device_ws): the
+// launch of a "shard" whose tiles are the list -- shard 0 of 1 of the whole frame's params, and the list as tile_map
+// (rp_units.h: shard tile k is frame tile tile_map[0 + k * 1]).  No stage of render_shard's scheduling runs: the tiles go
+// out in list order and nothing is measured.
+inline Refusal plan_tiles_launch(const rp_render_params* p, uint32_t n_listed, uint32_t n_frames, uint32_t frame_order,
+                                 const rp_scene_options& opt, LaunchPlan& out) {
+  if (!p) return {RP_EINVAL, "params is NULL"};
+  if (p->num_shards > 1 || p->shard != 0 || p->shard_map != RP_SHARD_INTERLEAVE)
+    return {RP_EINVAL, "a tile-list launch takes the whole frame's params: num_shards 0 or 1, shard 0, interleave"};
+  const Refusal r = plan_frame(p, n_frames, frame_order, opt, out);
+  if (r.code) return r;
+  if (p->spp == 0) return {RP_EINVAL, "a tile-list launch needs spp >= 1"};
+  if (out.t.nbatch != 1)
+    return {RP_EINVAL, "a tile-list launch renders one stream per pixel: samples_per_stream must be >= spp"};
+  if (n_listed > out.t.n_tiles) return {RP_EINVAL, "n_listed is above the frame's tile count"};
+  plan_tiles(n_listed, n_frames, frame_order, opt, out);  // (its slots: <= the frame's, which make_tiling admitted)
+  out.sortable = false;
+  out.measure = false;
   return {};
 }
 

@@ -6,8 +6,9 @@
 // A translation unit of its own, linked into librp.so and librp_diag.so and, like rp_accum.hip, not part of the
 // rp_build_id hash.  The render launch is host code only: the unchanged render kernel (rpk::launch_render) already
 // resolves a shard tile through tile_map and n_shard_tiles, so the list is handed to it as the tile map of a one-shard
-// launch of n_listed tiles (rp_tiles_plan.h: the arithmetic).  No stage of render_shard's scheduling runs and nothing is
-// measured: the workspace's learned state (tile costs, unit durations, plan, cost table) is neither read nor written.
+// launch of n_listed tiles (rp_schedule.h plan_tiles_launch: the arithmetic).  No stage of render_shard's scheduling runs
+// and nothing is measured: the workspace's learned state (tile costs, unit durations, plan, cost table) is neither read
+// nor written.
 //
 // tile_over_kernel: one block per listed tile.  A lane reads its pixel's 48 bytes (3 doubles of mean, 3 of variance) as
 // error_kernel does; the wave counts its pixels over by ballot and popcount, the block adds its four waves' counts
@@ -18,12 +19,9 @@
 // output list itself: position k of the output is never beyond entry k, and every flag is read before the barrier that
 // precedes the first write.  Both passes move a few megabytes next to a render launch of hundreds of milliseconds; they
 // are kept this simple on purpose (no vector loads, no second tile per block).
-#include "rp_state.h"  // first: the HIP runtime defines the qualifiers the shared headers use
-
-#include <cmath>
+#include "rp_pass.h"  // first: the HIP runtime defines the qualifiers the shared headers use
 
 #include "rp_accum.h"
-#include "rp_tiles_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -115,12 +113,6 @@ __global__ void __launch_bounds__(SCAN_BLOCK) compact_kernel(const SelArgs A) {
   if (threadIdx.x == 0) A.count[0] = total;
 }
 
-static bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
-
 }  // namespace rpt
 
 extern "C" {
@@ -139,28 +131,16 @@ int rp_render_tiles_device_ws(rp_scene* s, rp_workspace* w, const rp_camera* cam
   rpk::KParams& kp = lp.kp;
   const hipStream_t st = (hipStream_t)stream;
   DeviceGuard g(s->device);
-  // render_shard's wait on the workspace's last frame gather (another stream, perhaps): this launch touches none of
-  // what that gather reads or writes, but whichever launch follows a gather orders the workspace's streams the same way
-  if (w->gathered_pending) {
-    RP_HIP(hipStreamWaitEvent(st, w->ev_gathered.get(), 0));
-    w->gathered_pending = false;
-  }
-  RP_HIP(hipMemsetAsync(d_counters, 0, sizeof(uint64_t) * rpk::CTR_N, st));
+  // render_shard's prelude: this launch touches none of what a frame gather reads or writes, but whichever launch
+  // follows a gather orders the workspace's streams the same way
+  if ((rc = rpp::launch_begin(w, d_counters, st))) return rc;
   if (n_listed == 0) return RP_OK;
   refused = rps::launch_limits(lp, s->lanes());
   if (refused.code) return fail(refused.code, refused.msg);
-  std::memcpy(kp.orient, cam->orientation, sizeof kp.orient);
-  std::memcpy(kp.pos, cam->position, sizeof kp.pos);
-  kp.aspect = cam->aspect_ratio;
-  kp.tan_fov = std::tan(0.5 * cam->fov);
-  kp.focal = cam->focal_dist;
-  kp.lens = cam->lens_radius;
+  rpp::set_camera(kp, cam);
   kp.tile_map = d_tiles;  // shard tile k of the one-shard launch is frame tile d_tiles[k]
-  rpk::KScene ks = s->ks;
-  ks.rng_slab = reinterpret_cast<uint32_t*>(w->d_slab.get());
-  ks.spill = w->d_spill.get();
-  ks.unit_t0 = w->d_t0.get();  // (unread: nothing is measured)
-  RP_HIP(hipMemsetAsync(w->d_queue.get(), 0, sizeof(uint32_t) * rpk::QUEUE_WORDS, st));
+  rpk::KScene ks;         // (its unit_t0 is unread: nothing is measured)
+  if ((rc = rpp::launch_bind(s, w, ks, st))) return rc;
   RP_LAUNCH("tile-list render", rpk::launch_render(ks, kp, d_rgb, d_fg, d_counters, w->d_queue.get(),
                                                    rps::grid_for(kp.n_queue, s->resident()), stream));
   return RP_OK;
@@ -181,8 +161,8 @@ int rp_accum_tiles_select_device(const rp_render_params* p, const rp_error_param
   if (!(tile_share >= 0.0 && tile_share < 1.0)) return fail(RP_EINVAL, "tile_share must be in [0, 1)");
   if (n_in > (uint32_t)rpk::TILE_SORT_MAX) return fail(RP_EINVAL, "n_in is above 16384 (rpk::TILE_SORT_MAX)");
   const uint64_t list_bytes = 4ull * n_in;
-  if (rpt::overlaps(d_tiles_out, list_bytes, d_tiles_in, list_bytes) || rpt::overlaps(d_tiles_out, list_bytes, d_over, list_bytes) ||
-      rpt::overlaps(d_count, 4, d_tiles_out, list_bytes) || rpt::overlaps(d_count, 4, d_over, list_bytes))
+  if (rpp::overlaps(d_tiles_out, list_bytes, d_tiles_in, list_bytes) || rpp::overlaps(d_tiles_out, list_bytes, d_over, list_bytes) ||
+      rpp::overlaps(d_count, 4, d_tiles_out, list_bytes) || rpp::overlaps(d_count, 4, d_over, list_bytes))
     return fail(RP_EINVAL, "d_tiles_out must not alias d_tiles_in or d_over, nor d_count either output");
   rpt::SelArgs a;
   a.W = p->width, a.H = p->height, a.tw = t.tw, a.th = t.th, a.tiles_x = t.tiles_x, a.n_tiles = t.n_tiles, a.n_in = n_in;

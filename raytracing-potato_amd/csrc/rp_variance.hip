@@ -10,7 +10,7 @@
 // Kernel: one lane per shard slot (the render's compact shard order, rp_units.h slot_pixel's decode); a lane reads its
 // pixel's 3 B sums -- 24 B consecutive bytes -- twice (the second pass hits the cache) and writes 3 doubles.  Slots of
 // edge tiles outside the frame are not written.  No allocation, no synchronisation, one launch on the caller's stream.
-#include "rp_state.h"  // first: the HIP runtime defines the qualifiers the shared headers use
+#include "rp_pass.h"  // first: the HIP runtime defines the qualifiers the shared headers use
 
 #include "rp_units.h"
 #include "rp_variance.h"
@@ -21,21 +21,18 @@ namespace rpv {
 
 constexpr int VAR_BLOCK = 256;
 
-// the fields slot_pixel reads, under KParams' names, and the pass's own
 struct VarArgs {
-  uint32_t W, H, tw, th, shard, nshards, tiles_x;
+  rpp::ShardView v;
   uint32_t spp, sps, nbatch;
-  uint64_t n_slots;
-  const uint32_t* tile_map;  // the balanced plan's deal order (NULL = interleave)
   const double* partial;     // 3 per unit, unit = slot * nbatch + b
   double* var;               // 3 per slot
 };
 
 __global__ void __launch_bounds__(VAR_BLOCK) variance_kernel(const VarArgs A) {
   const uint64_t slot = (uint64_t)blockIdx.x * VAR_BLOCK + threadIdx.x;
-  if (slot >= A.n_slots) return;
+  if (slot >= A.v.n_slots) return;
   uint32_t pi, pj;
-  if (!rpk::slot_pixel(A, slot, pi, pj)) return;
+  if (!rpk::slot_pixel(A.v, slot, pi, pj)) return;
   const double* S = A.partial + 3 * slot * A.nbatch;
 #pragma unroll
   for (uint32_t c = 0; c < 3; c++) A.var[3 * slot + c] = batch_variance(S + c, 3, A.nbatch, A.spp, A.sps);
@@ -51,23 +48,16 @@ int rp_render_variance_device_ws(rp_scene* s, rp_workspace* w, const rp_render_p
   if (rc) return rc;
   if (!d_shard_var) return fail(RP_EINVAL, "d_shard_var is NULL");
   Tiling t;
-  if ((rc = frame_tiling(p, t))) return rc;
+  rpv::VarArgs a;
+  if ((rc = rpp::shard_view(w, p, t, a.v))) return rc;
   if (t.nbatch < 2)
     return fail(RP_EINVAL, "the variance needs at least two sample batches per pixel (spp > samples_per_stream)");
   const uint64_t units = t.n_slots * t.nbatch;
   if (3 * units > w->d_partial.capacity() || units > w->d_partial_hits.capacity())
     return fail(RP_EINVAL, "the workspace holds no batch sums of this shape: reserve it (rp_workspace_reserve) and "
                            "render the frame first");
-  // a balanced shard holds the tiles of the beauty shard rendered before it: the plan that render left in the workspace
-  if (t.balanced && !w->plan_matches(p, t))
-    return fail(RP_EINVAL, "no balanced plan for this frame in the workspace: render it first");
   if (t.n_slots == 0) return RP_OK;
-  rpv::VarArgs a;
-  a.W = p->width, a.H = p->height, a.tw = t.tw, a.th = t.th, a.shard = t.shard, a.nshards = t.shards;
-  a.tiles_x = t.tiles_x;
   a.spp = p->spp, a.sps = t.sps, a.nbatch = t.nbatch;
-  a.n_slots = t.n_slots;
-  a.tile_map = t.balanced ? w->d_plan.get() : nullptr;
   a.partial = w->d_partial.get();
   a.var = d_shard_var;
   DeviceGuard g(s->device);

@@ -13,10 +13,28 @@ from . import _ffi as F
 from .scene import RenderParams, Scene, shard_slot_count
 
 
+# scene_options' named values, by field
+_OPTION_NAMES = {
+    "builder": {"auto": F.RP_BUILDER_AUTO, "host": F.RP_BUILDER_HOST, "gpu": F.RP_BUILDER_DEVICE,
+                "ploc": F.RP_BUILDER_PLOC},
+    "tile_order": {"auto": F.RP_TILES_AUTO, "plain": F.RP_TILES_PLAIN, "cost": F.RP_TILES_COST,
+                   "morton": F.RP_TILES_MORTON, "probe": F.RP_TILES_PROBE},
+    "node_format": {"auto": F.RP_NODES_AUTO, "f32": F.RP_NODES_F32, "q8": F.RP_NODES_Q8, "w8": F.RP_NODES_W8},
+    "unit_queues": {"auto": F.RP_QUEUES_AUTO, "single": F.RP_QUEUES_SINGLE, "xcd_tiles": F.RP_QUEUES_XCD_TILES,
+                    "xcd_regions": F.RP_QUEUES_XCD_REGIONS},
+    "collapse": {"auto": F.RP_COLLAPSE_AUTO, "greedy": F.RP_COLLAPSE_GREEDY, "sah": F.RP_COLLAPSE_SAH},
+    "node_layout": {"auto": F.RP_LAYOUT_AUTO, "dfs": F.RP_LAYOUT_DFS, "dfs_line": F.RP_LAYOUT_DFS_LINE},
+    "unit_order": {"auto": F.RP_UNITS_AUTO, "tiles": F.RP_UNITS_TILES, "learned": F.RP_UNITS_LEARNED},
+}
+# the `order` argument of the multi-frame launches (RP_FRAME_ORDER_*); any other value is passed through
+_FRAME_ORDER = {"auto": F.RP_FRAME_ORDER_AUTO, "sequential": F.RP_FRAME_ORDER_SEQUENTIAL,
+                "interleaved": F.RP_FRAME_ORDER_INTERLEAVED, "pixel": F.RP_FRAME_ORDER_PIXEL}
+
+
 def scene_options(**kw) -> F.rp_scene_options:
     """rp_scene_options with the library defaults (rp_scene_options_init), fields overridden by keyword:
     builder ("auto" | "host" | "gpu" (LBVH) | "ploc" or RP_BUILDER_*), max_leaf, cost_traverse, always_max, lds_depth,
-    self_check, trav_threshold, tile_order, probe_n,
+    self_check, trav_threshold, probe_n,
     node_format ("auto" | "f32" | "q8" | "w8" or RP_NODES_*), tile_order ("auto" | "plain" | "cost" | "morton" | "probe"), leaf_break,
     unit_queues ("auto" | "single" | "xcd_tiles" | "xcd_regions" or RP_QUEUES_*), collapse ("auto" | "greedy" | "sah" or
     RP_COLLAPSE_*), node_layout ("auto" | "dfs" | "dfs_line" or RP_LAYOUT_*), unit_order ("auto" | "tiles" | "learned" or
@@ -24,27 +42,78 @@ def scene_options(**kw) -> F.rp_scene_options:
     o = F.rp_scene_options()
     F.check(F.rp().rp_scene_options_init(ctypes.byref(o)))
     for k, v in kw.items():
-        if k == "builder" and isinstance(v, str):
-            v = {"auto": F.RP_BUILDER_AUTO, "host": F.RP_BUILDER_HOST, "gpu": F.RP_BUILDER_DEVICE,
-                 "ploc": F.RP_BUILDER_PLOC}[v]
-        if k == "tile_order" and isinstance(v, str):
-            v = {"auto": F.RP_TILES_AUTO, "plain": F.RP_TILES_PLAIN, "cost": F.RP_TILES_COST,
-                 "morton": F.RP_TILES_MORTON, "probe": F.RP_TILES_PROBE}[v]
-        if k == "node_format" and isinstance(v, str):
-            v = {"auto": F.RP_NODES_AUTO, "f32": F.RP_NODES_F32, "q8": F.RP_NODES_Q8, "w8": F.RP_NODES_W8}[v]
-        if k == "unit_queues" and isinstance(v, str):
-            v = {"auto": F.RP_QUEUES_AUTO, "single": F.RP_QUEUES_SINGLE, "xcd_tiles": F.RP_QUEUES_XCD_TILES,
-                 "xcd_regions": F.RP_QUEUES_XCD_REGIONS}[v]
-        if k == "collapse" and isinstance(v, str):
-            v = {"auto": F.RP_COLLAPSE_AUTO, "greedy": F.RP_COLLAPSE_GREEDY, "sah": F.RP_COLLAPSE_SAH}[v]
-        if k == "node_layout" and isinstance(v, str):
-            v = {"auto": F.RP_LAYOUT_AUTO, "dfs": F.RP_LAYOUT_DFS, "dfs_line": F.RP_LAYOUT_DFS_LINE}[v]
-        if k == "unit_order" and isinstance(v, str):
-            v = {"auto": F.RP_UNITS_AUTO, "tiles": F.RP_UNITS_TILES, "learned": F.RP_UNITS_LEARNED}[v]
+        if isinstance(v, str) and k in _OPTION_NAMES:
+            v = _OPTION_NAMES[k][v]
         if not hasattr(o, k):
             raise KeyError(f"unknown scene option {k!r}")
         setattr(o, k, v)
     return o
+
+
+def _stream(stream, device):
+    """`stream` (a torch stream), or torch's current one on `device`."""
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(device)
+
+
+def _stream_ptr(stream, device=None):
+    """_stream(stream, device) as the library takes it."""
+    return ctypes.c_void_p(_stream(stream, device).cuda_stream)
+
+
+def _ws_handle(workspace, scene=None):
+    """The handle of `workspace` (None: the scene's own workspace); with `scene`, a live workspace of that scene."""
+    if workspace is None:
+        return None
+    assert scene is None or (workspace.scene is scene and workspace.handle)
+    return workspace.handle
+
+
+def _stats_dict(st) -> dict:
+    return {"rays": st.rays, "samples": st.samples, "pixels": st.pixels, "seconds": st.seconds}
+
+
+def _check_tensor(t, dtype, numel: int, device=None, contiguous: bool = True) -> None:
+    """`t` is a torch tensor on a GPU (on `device`, if given) of `dtype` and at least `numel` elements."""
+    assert t.dtype == dtype and t.is_cuda and t.numel() >= numel
+    assert not contiguous or t.is_contiguous()
+    assert device is None or t.device == device
+
+
+def _whole_frame(params, who: str) -> None:
+    if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
+        raise ValueError(f"{who} renders the whole frame on one device (num_shards = 1, interleave)")
+
+
+def _assemble(params, shard: dict, frame: dict, sp) -> None:
+    """rp_frame_assemble at num_shards = 1: every compact shard buffer of `shard` (torch f64) into frame order in the
+    tensor of `frame` under the same key, on the stream `sp` (_stream_ptr)."""
+    p, n = params.to_c(), shard_slot_count(params)
+    for k, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
+        F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 2 * (t.numel() // n), frame[k].data_ptr(), sp))
+
+
+def _progressive_args(params, who: str, frames_per_launch: int, max_frames: int, tol: float, share: float) -> None:
+    """What render_progressive and render_adaptive refuse alike."""
+    _whole_frame(params, who)
+    if not 1 <= frames_per_launch <= F.RP_MAX_FRAMES:
+        raise ValueError(f"frames_per_launch must be 1..{F.RP_MAX_FRAMES}, got {frames_per_launch}")
+    if min(frames_per_launch, max_frames) < 2:
+        raise ValueError("the variance needs two frames: frames_per_launch and max_frames must be >= 2")
+    if not (tol > 0.0 and 0.0 <= share <= 1.0):
+        raise ValueError(f"tol must be > 0 and share in [0, 1], got {tol}, {share}")
+
+
+def _progressive_state(params, frames_per_launch: int, dev) -> tuple:
+    """The device state of a progressive loop (allocated on torch's current stream): the launches' frames buffer, the
+    running mean, m2 and variance (compact shard buffers), the counters and the error statistics."""
+    import torch
+    n = shard_slot_count(params)
+    frames = torch.empty(frames_per_launch * 3 * n, dtype=torch.float64, device=dev)
+    mean, m2, var = (torch.empty(3 * n, dtype=torch.float64, device=dev) for _ in range(3))
+    ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
+    stats = torch.zeros(F.RP_ERROR_STATS_LEN, dtype=torch.int64, device=dev)
+    return frames, mean, m2, var, ctr, stats
 
 
 class DeviceScene:
@@ -119,12 +188,12 @@ class DeviceScene:
         """rp_workspace_reserve: device memory the asynchronous renders (and frame gathers) of `params`' shape
         need, in `workspace` (default: the scene's own)."""
         p = params.to_c()
-        F.check(F.rp().rp_workspace_reserve(self.handle, workspace.handle if workspace else None, ctypes.byref(p)))
+        F.check(F.rp().rp_workspace_reserve(self.handle, _ws_handle(workspace), ctypes.byref(p)))
 
     def reserve_frames(self, params: RenderParams, n_frames: int, workspace: "Workspace | None" = None) -> None:
         """rp_workspace_reserve_frames: rp_workspace_reserve, plus the batch sums of n_frames frames per launch."""
         p = params.to_c()
-        F.check(F.rp().rp_workspace_reserve_frames(self.handle, workspace.handle if workspace else None,
+        F.check(F.rp().rp_workspace_reserve_frames(self.handle, _ws_handle(workspace),
                                                    ctypes.byref(p), n_frames))
 
     def tile_map(self, params: RenderParams, workspace: "Workspace | None" = None) -> np.ndarray:
@@ -133,25 +202,24 @@ class DeviceScene:
         tiles = -(-params.width // params.tile_w) * -(-params.height // params.tile_h)
         out = np.empty(tiles, dtype=np.uint32)
         p = params.to_c()
-        F.check(F.rp().rp_workspace_tile_map(self.handle, workspace.handle if workspace else None, ctypes.byref(p),
+        F.check(F.rp().rp_workspace_tile_map(self.handle, _ws_handle(workspace), ctypes.byref(p),
                                              out.ctypes.data, tiles))
         return out
 
     def tile_costs(self, params: RenderParams, workspace: "Workspace | None" = None) -> np.ndarray:
         """rp_workspace_tile_costs: (2, shard tiles) measured costs of the last render in `workspace` -- summed unit
         durations per shard tile, then the longest unit."""
-        from .scene import shard_slot_count
         n = shard_slot_count(params) // (params.tile_w * params.tile_h)
         out = np.zeros(2 * max(n, 1), dtype=np.uint32)
         p = params.to_c()
-        F.check(F.rp().rp_workspace_tile_costs(self.handle, workspace.handle if workspace else None, ctypes.byref(p),
+        F.check(F.rp().rp_workspace_tile_costs(self.handle, _ws_handle(workspace), ctypes.byref(p),
                                                out.ctypes.data, len(out)))
         return out[:2 * n].reshape(2, n)
 
     def frame_info(self, workspace: "Workspace | None" = None) -> int:
         """rp_workspace_frame_info: RP_FRAME_* bits of the last render enqueued with `workspace` (None = the scene's)."""
         f = ctypes.c_uint32()
-        F.check(F.rp().rp_workspace_frame_info(self.handle, workspace.handle if workspace else None, ctypes.byref(f)))
+        F.check(F.rp().rp_workspace_frame_info(self.handle, _ws_handle(workspace), ctypes.byref(f)))
         return f.value
 
     def unit_order(self, n: int, workspace: "Workspace | None" = None) -> tuple:
@@ -159,7 +227,7 @@ class DeviceScene:
         frame_info has RP_FRAME_UNIT_ORDER)."""
         dur = np.zeros(n, dtype=np.uint32)
         order = np.zeros(n, dtype=np.uint32)
-        F.check(F.rp().rp_workspace_unit_order(self.handle, workspace.handle if workspace else None, dur.ctypes.data,
+        F.check(F.rp().rp_workspace_unit_order(self.handle, _ws_handle(workspace), dur.ctypes.data,
                                                order.ctypes.data, n))
         return dur, order
 
@@ -168,7 +236,7 @@ class DeviceScene:
         """rp_workspace_set_tile_costs: install a frame's learned cost table, (2, frame tiles) by frame tile."""
         c = np.ascontiguousarray(costs, dtype=np.uint32).reshape(-1)
         p = params.to_c()
-        F.check(F.rp().rp_workspace_set_tile_costs(self.handle, workspace.handle if workspace else None,
+        F.check(F.rp().rp_workspace_set_tile_costs(self.handle, _ws_handle(workspace),
                                                    ctypes.byref(p), c.ctypes.data, ranks))
 
     # ---- synchronous host-buffer render -----------------------------------------------------------
@@ -182,7 +250,7 @@ class DeviceScene:
         st = F.rp_stats()
         F.check(F.rp().rp_render(self.handle, ctypes.byref(cam), ctypes.byref(p), rgb.ctypes.data,
                                  fg.ctypes.data if fg is not None else None, ctypes.byref(st)))
-        return rgb, fg, {"rays": st.rays, "samples": st.samples, "pixels": st.pixels, "seconds": st.seconds}
+        return rgb, fg, _stats_dict(st)
 
     # ---- asynchronous device render (torch tensors, torch's current stream) ------------------------
     def render_device(self, params: RenderParams, out, counters, fg=None, camera=None, stream=None,
@@ -194,18 +262,16 @@ class DeviceScene:
         import torch
         cam = (camera or self.scene.camera).to_c()
         p = params.to_c()
-        assert out.dtype == torch.float64 and out.is_cuda and out.numel() >= 3 * shard_slot_count(params)
+        _check_tensor(out, torch.float64, 3 * shard_slot_count(params), contiguous=False)
         assert counters.dtype == torch.int64 and counters.numel() >= F.RP_COUNTERS_LEN
-        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        sp = _stream_ptr(stream, out.device)
         fgp = fg.data_ptr() if fg is not None else None
         if workspace is None:
             F.check(F.rp().rp_render_device(self.handle, ctypes.byref(cam), ctypes.byref(p), out.data_ptr(), fgp,
-                                            counters.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+                                            counters.data_ptr(), sp))
         else:
-            assert workspace.scene is self and workspace.handle
-            F.check(F.rp().rp_render_device_ws(self.handle, workspace.handle, ctypes.byref(cam), ctypes.byref(p),
-                                               out.data_ptr(), fgp, counters.data_ptr(),
-                                               ctypes.c_void_p(s.cuda_stream)))
+            F.check(F.rp().rp_render_device_ws(self.handle, _ws_handle(workspace, self), ctypes.byref(cam),
+                                               ctypes.byref(p), out.data_ptr(), fgp, counters.data_ptr(), sp))
 
     def render_frames_device(self, params: RenderParams, n_frames: int, out, counters, fg=None, camera=None,
                              stream=None, workspace: "Workspace | None" = None, order="auto") -> None:
@@ -218,18 +284,13 @@ class DeviceScene:
         cam = (camera or self.scene.camera).to_c()
         p = params.to_c()
         n = shard_slot_count(params)
-        assert out.dtype == torch.float64 and out.is_cuda and out.numel() >= 3 * n * n_frames
+        _check_tensor(out, torch.float64, 3 * n * n_frames, contiguous=False)
         assert fg is None or fg.numel() >= n * n_frames
         assert counters.dtype == torch.int64 and counters.numel() >= F.RP_COUNTERS_LEN
-        s = stream if stream is not None else torch.cuda.current_stream(out.device)
-        F.check(F.rp().rp_render_frames_device_ws(self.handle, workspace.handle if workspace else None,
-                                                  ctypes.byref(cam), ctypes.byref(p), n_frames,
-                                                  {"auto": F.RP_FRAME_ORDER_AUTO, "sequential": F.RP_FRAME_ORDER_SEQUENTIAL,
-                                                   "interleaved": F.RP_FRAME_ORDER_INTERLEAVED,
-                                                   "pixel": F.RP_FRAME_ORDER_PIXEL}.get(order, order),
-                                                  out.data_ptr(),
+        F.check(F.rp().rp_render_frames_device_ws(self.handle, _ws_handle(workspace), ctypes.byref(cam), ctypes.byref(p),
+                                                  n_frames, _FRAME_ORDER.get(order, order), out.data_ptr(),
                                                   fg.data_ptr() if fg is not None else None, counters.data_ptr(),
-                                                  ctypes.c_void_p(s.cuda_stream)))
+                                                  _stream_ptr(stream, out.device)))
 
     # ---- first-hit feature pass (rp_render_aov*): normal, albedo, depth, foreground ------------------
     def render_aov(self, params: RenderParams, camera=None, normal: bool = True, albedo: bool = True,
@@ -248,7 +309,7 @@ class DeviceScene:
         st = F.rp_stats()
         F.check(F.rp().rp_render_aov(self.handle, ctypes.byref(cam), ctypes.byref(p), ptr["normal"], ptr["albedo"],
                                      ptr["depth"], ptr["fg"], ctypes.byref(st)))
-        out["stats"] = {"rays": st.rays, "samples": st.samples, "pixels": st.pixels, "seconds": st.seconds}
+        out["stats"] = _stats_dict(st)
         return out
 
     def render_aov_device(self, params: RenderParams, normal=None, albedo=None, depth=None, fg=None, counters=None,
@@ -265,15 +326,12 @@ class DeviceScene:
         for t, dt, m in ((normal, torch.float64, 3 * n), (albedo, torch.float64, 3 * n), (depth, torch.float64, n),
                          (fg, torch.float32, n), (counters, torch.int64, F.RP_COUNTERS_LEN)):
             if t is not None:
-                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and t.numel() >= m
+                _check_tensor(t, dt, m)
                 dev = t.device
         assert dev is not None, "render_aov_device needs at least one output tensor"
-        if workspace is not None:
-            assert workspace.scene is self and workspace.handle
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
         ptr = [t.data_ptr() if t is not None else None for t in (normal, albedo, depth, fg, counters)]
-        F.check(F.rp().rp_render_aov_device_ws(self.handle, workspace.handle if workspace else None, ctypes.byref(cam),
-                                               ctypes.byref(p), *ptr, ctypes.c_void_p(s.cuda_stream)))
+        F.check(F.rp().rp_render_aov_device_ws(self.handle, _ws_handle(workspace, self), ctypes.byref(cam),
+                                               ctypes.byref(p), *ptr, _stream_ptr(stream, dev)))
 
     # ---- per-pixel variance from the batch sums (rp_render_variance_device_ws) -------------------------
     def render_variance_device(self, params: RenderParams, var, workspace: "Workspace | None" = None,
@@ -283,14 +341,10 @@ class DeviceScene:
         compact shard order like the render's rgb) on `stream` (torch stream; default: current).  Needs more than one
         sample batch per pixel (spp > samples_per_stream); order it after that render and before the workspace's next."""
         import torch
-        assert var.dtype == torch.float64 and var.is_cuda and var.is_contiguous()
-        assert var.numel() >= 3 * shard_slot_count(params)
-        if workspace is not None:
-            assert workspace.scene is self and workspace.handle
-        s = stream if stream is not None else torch.cuda.current_stream(var.device)
+        _check_tensor(var, torch.float64, 3 * shard_slot_count(params))
         p = params.to_c()
-        F.check(F.rp().rp_render_variance_device_ws(self.handle, workspace.handle if workspace else None,
-                                                    ctypes.byref(p), var.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+        F.check(F.rp().rp_render_variance_device_ws(self.handle, _ws_handle(workspace, self), ctypes.byref(p),
+                                                    var.data_ptr(), _stream_ptr(stream, var.device)))
 
     # ---- beauty + guides + denoiser, device-resident ---------------------------------------------------
     def render_denoised(self, params: RenderParams, denoise=None, bgra: bool = False, camera=None, stream=None,
@@ -306,14 +360,13 @@ class DeviceScene:
         denoise_var_params takes it); `params` must give more than one sample batch per pixel."""
         import torch
         from dataclasses import replace
-        if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
-            raise ValueError("render_denoised renders the whole frame on one device (num_shards = 1, interleave)")
+        _whole_frame(params, "render_denoised")
         if variance and params.spp <= (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM):
             raise ValueError("render_denoised(variance=True) needs at least two sample batches per pixel "
                              f"(spp > samples_per_stream): spp = {params.spp}, samples_per_stream = "
                              f"{params.samples_per_stream or F.RP_SAMPLES_PER_STREAM}")
         dev = torch.device("cuda", self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        s = _stream(stream, dev)
         w, h, n = params.width, params.height, shard_slot_count(params)
         self.reserve(params)
         with torch.cuda.stream(s):
@@ -327,10 +380,7 @@ class DeviceScene:
                 self.render_variance_device(params, shard["var"], stream=s)
             self.render_aov_device(params, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
                                    camera=camera, stream=s)
-            p = params.to_c()
-            for k, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
-                F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 2 * (t.numel() // n),
-                                                 frame[k].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+            _assemble(params, shard, frame, _stream_ptr(s))
             denoise_device(frame["rgb"], frame["normal"], frame["albedo"], frame["depth"], out, params=denoise,
                            stream=s, variance=frame.get("var"))
             if not bgra:
@@ -350,17 +400,13 @@ class DeviceScene:
         import torch
         n = shard_slot_count(params)
         for t in (mean, var):
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() >= 3 * n
-        assert stats.dtype == torch.int64 and stats.is_cuda and stats.is_contiguous()
-        assert stats.numel() >= F.RP_ERROR_STATS_LEN
-        if workspace is not None:
-            assert workspace.scene is self and workspace.handle
-        s = stream if stream is not None else torch.cuda.current_stream(mean.device)
+            _check_tensor(t, torch.float64, 3 * n)
+        _check_tensor(stats, torch.int64, F.RP_ERROR_STATS_LEN)
         p = params.to_c()
         e = F.rp_error_params(tol, eps)
-        F.check(F.rp().rp_accum_error_device_ws(self.handle, workspace.handle if workspace else None, ctypes.byref(p),
+        F.check(F.rp().rp_accum_error_device_ws(self.handle, _ws_handle(workspace, self), ctypes.byref(p),
                                                 ctypes.byref(e), mean.data_ptr(), var.data_ptr(), stats.data_ptr(),
-                                                ctypes.c_void_p(s.cuda_stream)))
+                                                _stream_ptr(stream, mean.device)))
 
     def render_progressive(self, params: RenderParams, frames_per_launch: int = 4, max_frames: int = 64,
                            tol: float = 0.05, share: float = 0.01, denoise=None, camera=None, stream=None) -> dict:
@@ -377,25 +423,15 @@ class DeviceScene:
         denoise_var_params takes it).  One device holds the whole frame (num_shards = 1, interleave)."""
         import torch
         from dataclasses import replace
-        if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
-            raise ValueError("render_progressive renders the whole frame on one device (num_shards = 1, interleave)")
-        if not 1 <= frames_per_launch <= F.RP_MAX_FRAMES:
-            raise ValueError(f"frames_per_launch must be 1..{F.RP_MAX_FRAMES}, got {frames_per_launch}")
-        if min(frames_per_launch, max_frames) < 2:
-            raise ValueError("the variance needs two frames: frames_per_launch and max_frames must be >= 2")
-        if not (tol > 0.0 and 0.0 <= share <= 1.0):
-            raise ValueError(f"tol must be > 0 and share in [0, 1], got {tol}, {share}")
+        _progressive_args(params, "render_progressive", frames_per_launch, max_frames, tol, share)
         dev = torch.device("cuda", self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        s = _stream(stream, dev)
         w, h, n = params.width, params.height, shard_slot_count(params)
         nbatch = -(-params.spp // (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM))
         self.reserve_frames(params, frames_per_launch)
         done, log = 0, []
         with torch.cuda.stream(s):
-            frames = torch.empty(frames_per_launch * 3 * n, dtype=torch.float64, device=dev)
-            mean, m2, var = (torch.empty(3 * n, dtype=torch.float64, device=dev) for _ in range(3))
-            ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
-            stats = torch.zeros(F.RP_ERROR_STATS_LEN, dtype=torch.int64, device=dev)
+            frames, mean, m2, var, ctr, stats = _progressive_state(params, frames_per_launch, dev)
             while done < max_frames:
                 k = min(frames_per_launch, max_frames - done)
                 q = replace(params, seed=(params.seed + done * nbatch * w * h) & 0xFFFFFFFFFFFFFFFF)
@@ -420,24 +456,18 @@ class DeviceScene:
         from dataclasses import replace
         dev = mean.device
         w, h, n = params.width, params.height, shard_slot_count(params)
-        p = params.to_c()
-        for key, t in (("mean", mean), ("variance", var)):
+        for key in ("mean", "variance"):
             out[key] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
-            F.check(F.rp().rp_frame_assemble(ctypes.byref(p), t.data_ptr(), 6, out[key].data_ptr(),
-                                             ctypes.c_void_p(s.cuda_stream)))
+        _assemble(params, {"mean": mean, "variance": var}, out, _stream_ptr(s))
         if denoise is False:
             return out
         ga = replace(params, spp=min(frames * params.spp, 64))
-        gp = ga.to_c()
-        guide = {}
-        shard = {k_: torch.empty(c * n, dtype=torch.float64, device=dev)
-                 for k_, c in (("normal", 3), ("albedo", 3), ("depth", 1))}
+        bufs = (("normal", 3), ("albedo", 3), ("depth", 1))
+        shard = {k_: torch.empty(c * n, dtype=torch.float64, device=dev) for k_, c in bufs}
         self.render_aov_device(ga, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
                                camera=camera, stream=s)
-        for k_, t in shard.items():  # 32-bit words per slot: 6 for 3 doubles, 2 for one
-            guide[k_] = torch.empty(t.numel() // n * w * h, dtype=torch.float64, device=dev)
-            F.check(F.rp().rp_frame_assemble(ctypes.byref(gp), t.data_ptr(), 2 * (t.numel() // n),
-                                             guide[k_].data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+        guide = {k_: torch.empty(c * w * h, dtype=torch.float64, device=dev) for k_, c in bufs}
+        _assemble(ga, shard, guide, _stream_ptr(s))
         out["denoised"] = torch.empty((h, w, 3), dtype=torch.float64, device=dev)
         denoise_device(out["mean"], guide["normal"], guide["albedo"], guide["depth"], out["denoised"],
                        params=denoise, stream=s, variance=out["variance"])
@@ -454,21 +484,16 @@ class DeviceScene:
         cam = (camera or self.scene.camera).to_c()
         p = params.to_c()
         slots = n_listed * (params.tile_w or 32) * (params.tile_h or 32)
-        assert tiles is None or (tiles.dtype == torch.int32 and tiles.is_cuda and tiles.is_contiguous()
-                                 and tiles.numel() >= n_listed)
-        assert out.dtype == torch.float64 and out.is_cuda and out.numel() >= 3 * slots * n_frames
+        if tiles is not None:
+            _check_tensor(tiles, torch.int32, n_listed)
+        _check_tensor(out, torch.float64, 3 * slots * n_frames, contiguous=False)
         assert fg is None or (fg.dtype == torch.float32 and fg.numel() >= slots * n_frames)
-        assert counters.dtype == torch.int64 and counters.is_cuda and counters.numel() >= F.RP_COUNTERS_LEN
-        if workspace is not None:
-            assert workspace.scene is self and workspace.handle
-        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        _check_tensor(counters, torch.int64, F.RP_COUNTERS_LEN, contiguous=False)
         F.check(F.rp().rp_render_tiles_device_ws(
-            self.handle, workspace.handle if workspace else None, ctypes.byref(cam), ctypes.byref(p),
-            tiles.data_ptr() if tiles is not None else None, n_listed, n_frames,
-            {"auto": F.RP_FRAME_ORDER_AUTO, "sequential": F.RP_FRAME_ORDER_SEQUENTIAL,
-             "interleaved": F.RP_FRAME_ORDER_INTERLEAVED, "pixel": F.RP_FRAME_ORDER_PIXEL}.get(order, order),
+            self.handle, _ws_handle(workspace, self), ctypes.byref(cam), ctypes.byref(p),
+            tiles.data_ptr() if tiles is not None else None, n_listed, n_frames, _FRAME_ORDER.get(order, order),
             out.data_ptr(), fg.data_ptr() if fg is not None else None, counters.data_ptr(),
-            ctypes.c_void_p(s.cuda_stream)))
+            _stream_ptr(stream, out.device)))
 
     def render_adaptive(self, params: RenderParams, frames_per_launch: int = 4, max_frames: int = 64,
                         max_launch_frames: int = 16, tol: float = 0.05, share: float = 0.01, tile_share=None,
@@ -488,23 +513,16 @@ class DeviceScene:
         pass and select (events on the stream)} and, unless denoise is False, "denoised" as render_progressive's."""
         import torch
         from dataclasses import replace
-        if params.num_shards != 1 or params.shard_map != F.RP_SHARD_INTERLEAVE:
-            raise ValueError("render_adaptive renders the whole frame on one device (num_shards = 1, interleave)")
-        if not 1 <= frames_per_launch <= F.RP_MAX_FRAMES:
-            raise ValueError(f"frames_per_launch must be 1..{F.RP_MAX_FRAMES}, got {frames_per_launch}")
+        _progressive_args(params, "render_adaptive", frames_per_launch, max_frames, tol, share)
         if not 1 <= max_launch_frames <= F.RP_MAX_FRAMES:
             raise ValueError(f"max_launch_frames must be 1..{F.RP_MAX_FRAMES}, got {max_launch_frames}")
-        if min(frames_per_launch, max_frames) < 2:
-            raise ValueError("the variance needs two frames: frames_per_launch and max_frames must be >= 2")
-        if not (tol > 0.0 and 0.0 <= share <= 1.0):
-            raise ValueError(f"tol must be > 0 and share in [0, 1], got {tol}, {share}")
         tile_share = share if tile_share is None else tile_share
         if not 0.0 <= tile_share < 1.0:
             raise ValueError(f"tile_share must be in [0, 1), got {tile_share}")
         if params.spp < 1 or (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM) < params.spp:
             raise ValueError("render_adaptive needs one stream per pixel: 1 <= spp <= samples_per_stream")
         dev = torch.device("cuda", self.device)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        s = _stream(stream, dev)
         w, h, n = params.width, params.height, shard_slot_count(params)
         tw, th = params.tile_w or 32, params.tile_h or 32
         tiles_x, tiles_y = -(-w // tw), -(-h // th)
@@ -515,10 +533,7 @@ class DeviceScene:
         tile_frames = np.zeros(T, dtype=np.int32)
         done, log, samples, rays = 0, [], 0, 0
         with torch.cuda.stream(s):
-            frames = torch.empty(frames_per_launch * 3 * n, dtype=torch.float64, device=dev)
-            mean, m2, var = (torch.empty(3 * n, dtype=torch.float64, device=dev) for _ in range(3))
-            ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
-            stats = torch.zeros(F.RP_ERROR_STATS_LEN, dtype=torch.int64, device=dev)
+            frames, mean, m2, var, ctr, stats = _progressive_state(params, frames_per_launch, dev)
             lists = [torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2)]
             count = torch.zeros(1, dtype=torch.int32, device=dev)
             cur, active, listed = None, T, np.arange(T)  # the list the next select reads: None = identity
@@ -560,12 +575,11 @@ class DeviceScene:
         f64) -> to_srgb_u8 bytes in TGA order B, G, R, A into `out` (torch uint8, >= 4 * slots)."""
         import torch
         n = shard_slot_count(params)
-        assert shard_rgb.dtype == torch.float64 and shard_rgb.is_cuda and shard_rgb.numel() >= 3 * n
-        assert out.dtype == torch.uint8 and out.is_cuda and out.numel() >= 4 * n
-        s = stream if stream is not None else torch.cuda.current_stream(out.device)
+        _check_tensor(shard_rgb, torch.float64, 3 * n, contiguous=False)
+        _check_tensor(out, torch.uint8, 4 * n, contiguous=False)
         p = params.to_c()
         F.check(F.rp().rp_shard_to_bgra8(self.handle, ctypes.byref(p), shard_rgb.data_ptr(), out.data_ptr(),
-                                         ctypes.c_void_p(s.cuda_stream)))
+                                         _stream_ptr(stream, out.device)))
 
     def frame_gather(self, comm: "Comm", params: RenderParams, shard_rgb, frame_bgra=None, frame_rgb=None,
                      counters=None, stream=None, workspace: "Workspace | None" = None) -> None:
@@ -573,36 +587,34 @@ class DeviceScene:
         other ranks' and de-interleaved into frame order: `frame_bgra` (torch uint8, W*H*4: to_srgb_u8 in
         tga::save order) and/or `frame_rgb` (torch f64, W*H*3); `counters` (int64, 4) summed over ranks."""
         import torch
-        s = stream if stream is not None else torch.cuda.current_stream(shard_rgb.device)
         n = params.width * params.height
         if frame_bgra is not None:
-            assert frame_bgra.dtype == torch.uint8 and frame_bgra.is_cuda and frame_bgra.numel() >= 4 * n
+            _check_tensor(frame_bgra, torch.uint8, 4 * n, contiguous=False)
         if frame_rgb is not None:
-            assert frame_rgb.dtype == torch.float64 and frame_rgb.is_cuda and frame_rgb.numel() >= 3 * n
+            _check_tensor(frame_rgb, torch.float64, 3 * n, contiguous=False)
         p = params.to_c()
-        F.check(F.rp().rp_frame_gather(comm.handle, self.handle, workspace.handle if workspace else None,
+        F.check(F.rp().rp_frame_gather(comm.handle, self.handle, _ws_handle(workspace),
                                        ctypes.byref(p), shard_rgb.data_ptr(),
                                        frame_bgra.data_ptr() if frame_bgra is not None else None,
                                        frame_rgb.data_ptr() if frame_rgb is not None else None,
                                        counters.data_ptr() if counters is not None else None,
-                                       ctypes.c_void_p(s.cuda_stream)))
+                                       _stream_ptr(stream, shard_rgb.device)))
 
     def frames_gather(self, comm: "Comm", params: RenderParams, n_frames: int, shard_rgb, frames_bgra=None,
                       counters=None, stream=None, workspace: "Workspace | None" = None) -> None:
         """rp_frames_gather: the n_frames shards of one render_frames_device launch (`shard_rgb`, back to back) in one
         all-gather; `frames_bgra` (torch uint8, n_frames * W*H*4) receives the assembled frames back to back."""
         import torch
-        s = stream if stream is not None else torch.cuda.current_stream(shard_rgb.device)
         n = params.width * params.height
         if frames_bgra is not None:
-            assert frames_bgra.dtype == torch.uint8 and frames_bgra.is_cuda and frames_bgra.numel() >= 4 * n * n_frames
+            _check_tensor(frames_bgra, torch.uint8, 4 * n * n_frames, contiguous=False)
         assert shard_rgb.dtype == torch.float64 and shard_rgb.numel() >= 3 * shard_slot_count(params) * n_frames
         p = params.to_c()
-        F.check(F.rp().rp_frames_gather(comm.handle, self.handle, workspace.handle if workspace else None,
+        F.check(F.rp().rp_frames_gather(comm.handle, self.handle, _ws_handle(workspace),
                                         ctypes.byref(p), n_frames, shard_rgb.data_ptr(),
                                         frames_bgra.data_ptr() if frames_bgra is not None else None,
                                         counters.data_ptr() if counters is not None else None,
-                                        ctypes.c_void_p(s.cuda_stream)))
+                                        _stream_ptr(stream, shard_rgb.device)))
 
     def frames_block_words(self, params: RenderParams, n_frames: int) -> int:
         """rp_frames_block_words: 32-bit words of one rank's packed block for a launch of n_frames frames (the same on
@@ -618,41 +630,36 @@ class DeviceScene:
         (output stage to BGRA8) and its counters into `send` (torch int32, frames_block_words words), for a caller's
         own all-gather."""
         import torch
-        s = stream if stream is not None else torch.cuda.current_stream(shard_rgb.device)
-        assert send.dtype == torch.int32 and send.is_cuda and send.numel() >= self.frames_block_words(params, n_frames)
+        _check_tensor(send, torch.int32, self.frames_block_words(params, n_frames), contiguous=False)
         p = params.to_c()
-        F.check(F.rp().rp_frames_pack(self.handle, workspace.handle if workspace else None, ctypes.byref(p), n_frames,
+        F.check(F.rp().rp_frames_pack(self.handle, _ws_handle(workspace), ctypes.byref(p), n_frames,
                                       shard_rgb.data_ptr(), counters.data_ptr(), send.data_ptr(),
-                                      ctypes.c_void_p(s.cuda_stream)))
+                                      _stream_ptr(stream, shard_rgb.device)))
 
     def frames_unpack(self, params: RenderParams, n_frames: int, recv, frames_bgra, counters=None, stream=None,
                       workspace: "Workspace | None" = None) -> None:
         """rp_frames_unpack: the all-gathered blocks of every rank (`recv`, rank-major) de-interleaved into the n_frames
         assembled BGRA8 frames and the counters summed over the ranks."""
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream(recv.device)
         n = params.width * params.height
         assert frames_bgra.is_cuda and frames_bgra.numel() * frames_bgra.element_size() >= 4 * n * n_frames
         p = params.to_c()
-        F.check(F.rp().rp_frames_unpack(self.handle, workspace.handle if workspace else None, ctypes.byref(p), n_frames,
+        F.check(F.rp().rp_frames_unpack(self.handle, _ws_handle(workspace), ctypes.byref(p), n_frames,
                                         recv.data_ptr(), frames_bgra.data_ptr(),
                                         counters.data_ptr() if counters is not None else None,
-                                        ctypes.c_void_p(s.cuda_stream)))
+                                        _stream_ptr(stream, recv.device)))
 
     def render_gather(self, comm: "Comm", params: RenderParams, frame_bgra=None, frame_rgb=None, counters=None,
                       camera=None, stream=None, workspace: "Workspace | None" = None) -> None:
         """rp_render_gather: render this rank's shard and gather the frame (see frame_gather)."""
-        import torch
         dev = (frame_bgra if frame_bgra is not None else frame_rgb).device
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
         cam = (camera or self.scene.camera).to_c()
         p = params.to_c()
-        F.check(F.rp().rp_render_gather(comm.handle, self.handle, workspace.handle if workspace else None,
+        F.check(F.rp().rp_render_gather(comm.handle, self.handle, _ws_handle(workspace),
                                         ctypes.byref(cam), ctypes.byref(p),
                                         frame_bgra.data_ptr() if frame_bgra is not None else None,
                                         frame_rgb.data_ptr() if frame_rgb is not None else None,
                                         counters.data_ptr() if counters is not None else None,
-                                        ctypes.c_void_p(s.cuda_stream)))
+                                        _stream_ptr(stream, dev)))
 
     def intersect(self, rays: np.ndarray):
         """Hittable::hit on the root for (n, 8) rays -> ((n, 9) hits, (n,) material ids)."""
@@ -734,7 +741,7 @@ class MultiScene:
         F.check(F.rp().rp_render_multi(self.handle, ctypes.byref(cam), ctypes.byref(p),
                                        out.ctypes.data if out is not None else None,
                                        ob.ctypes.data if ob is not None else None, ctypes.byref(st)))
-        return out, ob, {"rays": st.rays, "samples": st.samples, "pixels": st.pixels, "seconds": st.seconds}
+        return out, ob, _stats_dict(st)
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -920,14 +927,13 @@ def accum_frames_device(frames, n_frames: int, mean, m2, n_prior: int = 0, var=N
     import torch
     for t in (frames, mean, m2, var):
         if t is not None:
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.device == mean.device
+            _check_tensor(t, torch.float64, 0, device=mean.device)
     small = min(t.numel() for t in (mean, m2, var) if t is not None)
     n_words, stride = _accum_shape(n_frames, n_words, stride, small, frames.numel())
-    s = stream if stream is not None else torch.cuda.current_stream(mean.device)
     with torch.cuda.device(mean.device):
         F.check(F.rp().rp_accum_frames_device(n_words, n_prior, n_frames, frames.data_ptr(), stride, mean.data_ptr(),
                                               m2.data_ptr(), var.data_ptr() if var is not None else None,
-                                              ctypes.c_void_p(s.cuda_stream)))
+                                              _stream_ptr(stream, mean.device)))
 
 
 def accum_frames_host(frames, n_frames: int, mean, m2, n_prior: int = 0, var=None, n_words=None, stride=None) -> None:
@@ -974,20 +980,19 @@ def accum_tiles_select_device(params: RenderParams, mean, var, tiles_out, count,
     import torch
     n = shard_slot_count(params)
     for t in (mean, var):
-        assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.numel() >= 3 * n
+        _check_tensor(t, torch.float64, 3 * n)
     if n_in is None:
         n_in = tiles_in.numel() if tiles_in is not None else n // ((params.tile_w or 32) * (params.tile_h or 32))
     for t, m in ((tiles_in, n_in), (over, n_in), (tiles_out, n_in), (count, 1)):
-        assert t is None or (t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() >= m
-                             and t.device == mean.device)
-    s = stream if stream is not None else torch.cuda.current_stream(mean.device)
+        if t is not None:
+            _check_tensor(t, torch.int32, m, device=mean.device)
     p = params.to_c()
     e = F.rp_error_params(tol, eps)
     with torch.cuda.device(mean.device):
         F.check(F.rp().rp_accum_tiles_select_device(
             ctypes.byref(p), ctypes.byref(e), tile_share, mean.data_ptr(), var.data_ptr(),
             tiles_in.data_ptr() if tiles_in is not None else None, n_in, over.data_ptr() if over is not None else None,
-            tiles_out.data_ptr(), count.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+            tiles_out.data_ptr(), count.data_ptr(), _stream_ptr(stream, mean.device)))
 
 
 def accum_tiles_select_host(params: RenderParams, mean, var, tiles_in=None, n_in=None, tol: float = 0.0,
@@ -1036,17 +1041,16 @@ def accum_frames_tiles_device(frames, n_frames: int, tiles, n_listed: int, tile_
     import torch
     for t in (frames, mean, m2, var):
         if t is not None:
-            assert t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.device == mean.device
-    assert tiles is None or (tiles.dtype == torch.int32 and tiles.is_cuda and tiles.is_contiguous()
-                             and tiles.numel() >= n_listed and tiles.device == mean.device)
+            _check_tensor(t, torch.float64, 0, device=mean.device)
+    if tiles is not None:
+        _check_tensor(tiles, torch.int32, n_listed, device=mean.device)
     small = min(t.numel() for t in (mean, m2, var) if t is not None)
     stride, n_state_tiles = _tiles_shape(n_frames, n_listed, tile_words, stride, n_state_tiles, small, frames.numel())
-    s = stream if stream is not None else torch.cuda.current_stream(mean.device)
     with torch.cuda.device(mean.device):
         F.check(F.rp().rp_accum_frames_tiles_device(
             tile_words, n_state_tiles, tiles.data_ptr() if tiles is not None else None, n_listed, n_prior, n_frames,
             frames.data_ptr(), stride, mean.data_ptr(), m2.data_ptr(), var.data_ptr() if var is not None else None,
-            ctypes.c_void_p(s.cuda_stream)))
+            _stream_ptr(stream, mean.device)))
 
 
 def accum_frames_tiles_host(frames, n_frames: int, tiles, n_listed: int, tile_words: int, mean, m2, n_prior: int = 0,
@@ -1081,7 +1085,7 @@ def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, s
         if t is not None:
             assert t.dtype == torch.float64 and t.device == out.device and t.is_contiguous() and t.numel() == m
     assert rgb is not None
-    s = stream if stream is not None else torch.cuda.current_stream(out.device)
+    s = _stream(stream, out.device)
     need = denoise_scratch_bytes(w, h) if variance is None else denoise_var_scratch_bytes(w, h)
     if scratch is None:
         with torch.cuda.stream(s):
@@ -1092,11 +1096,11 @@ def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, s
         if variance is None:
             p = denoise_params(params)
             F.check(F.rp().rp_denoise_device(ctypes.byref(p), w, h, rgb.data_ptr(), *gp, out.data_ptr(),
-                                             scratch.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+                                             scratch.data_ptr(), _stream_ptr(s)))
         else:
             p = denoise_var_params(params)
             F.check(F.rp().rp_denoise_var_device(ctypes.byref(p), w, h, rgb.data_ptr(), variance.data_ptr(), *gp,
-                                                 out.data_ptr(), scratch.data_ptr(), ctypes.c_void_p(s.cuda_stream)))
+                                                 out.data_ptr(), scratch.data_ptr(), _stream_ptr(s)))
 
 
 def tga_bytes(width: int, height: int, bgra) -> bytes:

@@ -1,7 +1,7 @@
 """Tile-adaptive progressive rendering on the CPU: the host models rph_accum_tiles_select and
 rph_accum_frames_tiles (plain loops over csrc/rp_accum.h, the header the kernels compile) against the numpy models of
 tests/accum_tiles_ref.py -- values bit for bit, counts and lists exact --, the launch arithmetic of a tile-list launch
-(csrc/rp_tiles_plan.h) against rps::plan_launch, and the render kernel's own unit fetch (csrc/rp_units.h) walked on the
+(csrc/rp_schedule.h plan_tiles_launch) against rps::plan_launch, and the render kernel's own unit fetch (csrc/rp_units.h) walked on the
 CPU with a foreign tile list as its tile map: every (listed tile, in-frame pixel, frame) exactly once, at the slot
 rp_render_tiles_device_ws's layout gives it, and nothing else."""
 import ctypes

@@ -389,7 +389,7 @@ static void check_denoise() {
               "and a negative tolerance refused\n");
 }
 
-// tile-adaptive progressive rendering's host code (csrc/rp_accum.h and csrc/rp_tiles_plan.h: rph_accum_frames_tiles,
+// tile-adaptive progressive rendering's host code (csrc/rp_accum.h and csrc/rp_schedule.h: rph_accum_frames_tiles,
 // rph_accum_tiles_select, rph_plan_tiles_launch, rph_tiles_unit_walk) on a 37 x 21 frame in 8 x 4 tiles (5 x 6 tiles,
 // both edges ragged), every buffer exactly sized: the fold and the select over a shuffled list with an entry outside
 // the frame, the compaction in place, the plan over every list length and the fetch over the foreign list
