@@ -93,7 +93,8 @@ __global__ void __launch_bounds__(BLOCK) aov_kernel(const AovArgs args) {
     V3 o, d;
     camera_dir(A, ju, jv, dx, dy, o, d);
     HitRec hr;
-    traverse<NF>(S, stk, BLOCK, o, d, RAY_EPSILON, INF, hr, overflow);  // root.hit(ray), t_min 1e-3, t_max +inf
+    // root.hit(ray), t_min 1e-3, t_max +inf (the always-tested records per lane: rp_device.h trav_begin)
+    traverse<NF, false>(S, stk, BLOCK, o, d, RAY_EPSILON, INF, hr, overflow);
     if (hr.prim >= 0) {  // a miss adds zero to every sum (render.rs:119)
       hits++;
       dep = dep + hr.t;

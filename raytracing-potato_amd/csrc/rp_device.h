@@ -665,13 +665,59 @@ RPK_INLINE void prim_test(const KScene& S, uint32_t k, V3 o, V3 d, double tmin, 
 // primitive for every starting lane, instead of a divergent leaf test deep in the prim loop; their hit
 // also bounds the traversal from the root.  The closest hit is the tree's (any test order, up to exact-t
 // ties).
-template <uint32_t NF>
+//
+// The list is the same for every lane and never written during a launch, so its records come through the constant
+// address space: scalar loads into SGPRs, no per-lane copy of a record in VGPRs.  A sphere reads its centre, radius
+// and {kind, material} (ten dwords); the next record's loads are issued in front of the current test, so the site
+// waits for memory once, in front of its first test (waiting once per record instead measured the same on C3:
+// profiles/r24/headline_ab.json).  The kind is a scalar and its branch wave-uniform: a sphere goes to
+// rpi::sphere_test with its constants as scalar operands and the closest hit is taken in that test's one masked
+// block, in place.  A record that is no sphere (a huge triangle the size rule listed) ends the sphere loop: it and the
+// rest of the list, in list order, take prim_test as the leaf loop has it -- with that path inside the sphere loop the
+// two paths' hit records meet behind every test, and the closest hit is copied in and out around each sphere's block.
+typedef __attribute__((address_space(4))) const rpl::Prim cst_prim;
+struct AlwaysRec {
+  double cx, cy, cz, r;
+  uint32_t kind, mat;
+};
+RPK_INLINE AlwaysRec always_load(const KScene& S, uint32_t k) {
+  const cst_prim* p = (const cst_prim*)S.prims + k;
+  return {p->g[0], p->g[1], p->g[2], p->g[3], p->kind, p->material};
+}
+RPK_INLINE void always_tests(const KScene& S, V3 o, V3 d, double tmin, double& best, TravState& ts) {
+  if (S.n_always == 0) return;
+  const uint32_t last = S.always_first + S.n_always - 1;
+  uint32_t k = S.always_first;
+  AlwaysRec nx = always_load(S, k);
+  for (; k <= last; k++) {
+    const AlwaysRec p = nx;
+    if (p.kind != rpl::PRIM_SPHERE) break;
+    nx = always_load(S, min(k + 1, last));
+    DREG(DREG_ALWAYS)
+    rpi::sphere_test(v3(p.cx, p.cy, p.cz), p.r, o, d, tmin, best, [&](double t) {
+      best = t; ts.bestp = (int32_t)k; ts.bestm = p.mat;
+    });
+  }
+  for (; k <= last; k++) {
+    DREG(DREG_ALWAYS)
+    prim_test<false>(S, k, o, d, tmin, best, ts);
+  }
+}
+
+// SCALAR = false (the feature pass): the records through prim_test's per-lane loads.  That kernel keeps its KScene in
+// SGPRs across its sample loop and spills them at the limit of 106; with the records in SGPRs as well its q8
+// instantiation goes from 127 to 129 VGPRs and from 4 waves per SIMD to 3.
+template <uint32_t NF, bool SCALAR = true>
 RPK_INLINE void trav_begin(const KScene& S, V3 o, V3 d, double tmin, double tmax, TravState& t) {
   trav_init<NF>(S, tmax, t, d);
   double best = t.best;
-  for (uint32_t k = S.always_first; k < S.always_first + S.n_always; k++) {
-    DREG(DREG_ALWAYS)
-    prim_test<false>(S, k, o, d, tmin, best, t);
+  if constexpr (SCALAR) {
+    always_tests(S, o, d, tmin, best, t);
+  } else {
+    for (uint32_t k = S.always_first; k < S.always_first + S.n_always; k++) {
+      DREG(DREG_ALWAYS)
+      prim_test<false>(S, k, o, d, tmin, best, t);
+    }
   }
   t.best = best;
 }
@@ -1052,13 +1098,13 @@ RPK_INLINE void trav_step(const KScene& S, lds_u32* stk, uint32_t stride, uint32
   ts.leaf = leaf;
 }
 
-template <uint32_t NF>
+template <uint32_t NF, bool SCALAR = true>
 RPK_INLINE void traverse(const KScene& S, lds_u32* stk, uint32_t stride, V3 o, V3 d, double tmin, double tmax,
                          HitRec& hr, bool& overflow, TravDiag* td = nullptr) {
   Ray32 r;
   setup_ray32<NF>(o, d, tmin, S.qbound, r);
   TravState t;
-  trav_begin<NF>(S, o, d, tmin, tmax, t);
+  trav_begin<NF, SCALAR>(S, o, d, tmin, tmax, t);
   while (!trav_done(t)) trav_step<false, NF>(S, stk, stride, 0u, r, o, d, tmin, t, overflow, td);
   hr.t = t.best;
   hr.u = t.bu;

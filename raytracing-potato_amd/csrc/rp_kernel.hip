@@ -156,10 +156,7 @@ __global__ void __launch_bounds__(BLOCK) RPK_RENDER_ATTR render_kernel(const KAr
       if (newray) {
         DCYC_BEGIN(cn)
         double best = ts.best;
-        for (uint32_t k = S.always_first; k < S.always_first + S.n_always; k++) {
-          DREG(DREG_ALWAYS)
-          prim_test<false>(S, k, o, d, RAY_EPSILON, best, ts);
-        }
+        always_tests(S, o, d, RAY_EPSILON, best, ts);
         ts.best = best;
         newray = false;
         DCYC_END(DCYC_NEWRAY, cn)
