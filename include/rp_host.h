@@ -141,6 +141,17 @@ int rph_ray_setup(uint32_t node_format, double qbound, const double* rays, uint6
  * (a sphere's u and v are 0), zeros for a rejected one.  RP_EINVAL for a NULL pointer or an unknown kind. */
 int rph_prim_test(uint32_t kind, const double g[9], const double* rays, uint64_t n, double* out);
 
+/* Test hooks: the packed head of a device material record (raytracing-potato_amd/csrc/rp_layout.h material_head_pack /
+ * material_head_unpack, the one pair the scene builder and the render kernel's shading compile).
+ * rph_material_head packs fields = {scatter_kind, absorb_kind, emit_kind, needs_uv, absorb_tex, emit_tex} into
+ * packed = {head, head_tex} and unpacks those again into unpacked = {the same six, wide}; with wide = 1 the head holds
+ * no texture ids (one of them needs more than 16 bits) and unpacked[4..5] mean nothing.
+ * rph_scene_materials builds desc's shading tables and writes, for the first min(cap, n) of its n materials, the
+ * record's first eight words as the device gets them: {scatter_kind, absorb_kind, emit_kind, absorb_tex, emit_tex,
+ * needs_uv, head, head_tex}; *n_materials = n.  RP_EINVAL for a NULL pointer or a scene the builder refuses. */
+int rph_material_head(const uint32_t fields[6], uint32_t packed[2], uint32_t unpacked[7]);
+int rph_scene_materials(const rp_scene_desc* desc, uint64_t cap, uint32_t* words, uint64_t* n_materials);
+
 /* Test hook: the render kernel's unit fetch, run on the CPU (raytracing-potato_amd/csrc/rp_units.h fetch_pixel, unit_frame
  * and unit_spp: the same header the kernel compiles, in a host environment that stands in for the kernarg segment, the
  * atomics and the wave).  The launch is planned by rps::plan_launch from the arguments rph_plan_launch takes (and must

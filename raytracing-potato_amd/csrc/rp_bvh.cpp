@@ -743,6 +743,10 @@ int validate(const rp_scene_desc* d, std::string& err) {
   if (d->n_materials && !d->materials) return fail("materials is NULL");
   // the kernel carries a hit's material in 31 bits beside its primitive kind (rp_device.h HitRec::km)
   if (d->n_materials >= 0x7FFFFFFFu) return fail("too many materials (>= 2^31 - 1)");
+  // shading addresses material and texture records by 32-bit byte offsets (rp_device.h mat_at, tex_at)
+  if ((uint64_t)d->n_materials * sizeof(rpl::Material) > 0xFFFFFFFFull ||
+      (uint64_t)d->n_textures * sizeof(rpl::Texture) > 0xFFFFFFFFull)
+    return fail("too many materials or textures for 32-bit device offsets");
   if (d->n_textures && !d->textures) return fail("textures is NULL");
   auto check_tex = [&](uint32_t t, const char* what) -> bool {
     if (t >= d->n_textures) { err = std::string(what) + ": TextureId out of range"; return false; }
@@ -857,6 +861,7 @@ int build(const rp_scene_desc* d, const BuildOptions& opt, PackedScene& out, std
       m.absorb_color[k] = s.absorb.color[k];
       m.emit_color[k] = s.emit.color[k];
     }
+    rpl::material_head_pack(m, m.head, m.head_tex);  // the control words once more, for shading's one load
     out.materials.push_back(m);
   }
   if (out.materials.empty()) out.materials.push_back(rpl::Material{});

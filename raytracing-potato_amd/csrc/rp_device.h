@@ -1122,14 +1122,20 @@ struct Surf {
 
 // uv is computed only when the hit material reads it (rpl::Material::needs_uv): same values, and the
 // f64 atan2/asin of a sphere hit are skipped for untextured spheres (the ground).
-RPK_INLINE bool surface(const KScene& S, const HitRec& hr, V3 o, V3 d, Surf& s, bool force_uv = false) {
+//
+// surface_at is the record for a caller that already holds the hit's material (s.material) and can tell whether it
+// reads uv (shade_ray: from the material's head, asked for only where a path needs the answer, so that the head's load
+// is not waited for in front of the surface's own first load); surface() finds both itself.
+RPK_INLINE uint32_t hit_material(const KScene& S, const HitRec& hr) {
+  return hr.km != KM_UNKNOWN ? hr.km & ~KM_TRIANGLE : S.prims[hr.prim].material;
+}
+template <class F>
+RPK_INLINE bool surface_at(const KScene& S, const HitRec& hr, V3 o, V3 d, Surf& s, F need_uv) {
   const rpl::Prim* p = S.prims + hr.prim;
   s.p = add(o, smul(hr.t, d));  // Ray::at (utility.rs:67)
   const bool known = hr.km != KM_UNKNOWN;
-  s.material = known ? hr.km & ~KM_TRIANGLE : p->material;
   s.u = 0.0;
   s.v = 0.0;
-  const bool need_uv = force_uv || S.mats[s.material].needs_uv != 0;
   if (known ? (hr.km & KM_TRIANGLE) != 0 : p->kind == rpl::PRIM_TRIANGLE) {
     const double u = hr.u, v = hr.v, w = 1.0 - u - v;
     const rpl::PrimRef& pr = S.prim_refs[hr.prim];
@@ -1138,19 +1144,32 @@ RPK_INLINE bool surface(const KScene& S, const HitRec& hr, V3 o, V3 d, Surf& s, 
     const V3 n1 = v3(S.vnrm[3 * i1], S.vnrm[3 * i1 + 1], S.vnrm[3 * i1 + 2]);
     const V3 n2 = v3(S.vnrm[3 * i2], S.vnrm[3 * i2 + 1], S.vnrm[3 * i2 + 2]);
     s.n = add(add(smul(w, n0), smul(u, n1)), smul(v, n2));
-    if (need_uv) {
+    if (need_uv()) {
       s.u = (w * S.vuv[2 * i0] + u * S.vuv[2 * i1]) + v * S.vuv[2 * i2];
       s.v = (w * S.vuv[2 * i0 + 1] + u * S.vuv[2 * i1 + 1]) + v * S.vuv[2 * i2 + 1];
     }
   } else {
     const V3 c = v3(p->g[0], p->g[1], p->g[2]);
     s.n = normalize(sub(s.p, c));
-    return need_uv;  // the caller computes the sphere uv (shared site)
+    return need_uv();  // the caller computes the sphere uv (shared site)
   }
   return false;
 }
+RPK_INLINE bool surface(const KScene& S, const HitRec& hr, V3 o, V3 d, Surf& s, bool force_uv = false) {
+  s.material = hit_material(S, hr);
+  const bool need_uv = force_uv || S.mats[s.material].needs_uv != 0;
+  return surface_at(S, hr, o, d, s, [&] { return need_uv; });
+}
 
 // ------------------------------------------------------------------ shading ----------------------
+
+// A word of a material or texture record: 32-bit byte offset from the wave-uniform table base (scalar-base +
+// vector-offset loads, as nodes and primitives are read; the builder refuses tables beyond 4 GB).
+template <class T>
+RPK_INLINE T rec_load(const void* base, uint32_t off) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
+}
+RPK_INLINE uint32_t mat_at(uint32_t material) { return material * (uint32_t)sizeof(rpl::Material); }
 
 // x / 255.0 for a byte x, correctly rounded without a division: q0 = x * fl(1/255) is off by at most
 // one ulp and one FMA residual step corrects it (exhaustively checked for all 256 x, tests/test_host.py).
@@ -1162,11 +1181,24 @@ RPK_INLINE double u8_unit(uint32_t x) {
 
 // texture.rs:51-60: walk Checker indirections down to the texture that produces the value
 // (validate() guarantees the walk terminates).
-RPK_INLINE uint32_t tex_resolve(const KScene& S, uint32_t tid, const Surf& h) {
-  while (S.texs[tid].kind == 4) {
-    const rpl::Texture& t = S.texs[tid];
+// A record's first four words {kind, odd, even, width} come as one 16 B load, so a level of the walk waits for memory
+// once; `th` returns the resolved texture's, whose kind and width the callers go on with instead of reading them again.
+RPK_INLINE uint32_t tex_at(uint32_t tid) { return tid * (uint32_t)sizeof(rpl::Texture); }
+RPK_INLINE uint4 tex_head(const KScene& S, uint32_t tid) {
+  static_assert(offsetof(rpl::Texture, kind) == 0 && offsetof(rpl::Texture, odd) == 4 && offsetof(rpl::Texture, even) == 8 &&
+                offsetof(rpl::Texture, width) == 12, "Texture head");
+  const uint4 t = rec_load<uint4>(S.texs, tex_at(tid));
+  // (all four words count as read here: left to itself the compiler narrows the load to the kind and fetches the
+  // children and the width by loads of their own, each behind its own wait)
+  asm volatile("" : : "v"(t.x), "v"(t.y), "v"(t.z), "v"(t.w));
+  return t;
+}
+RPK_INLINE uint32_t tex_resolve(const KScene& S, uint32_t tid, const Surf& h, uint4& th) {
+  th = tex_head(S, tid);
+  while (th.x == 4) {
     const double s = floor(h.p.x) + floor(h.p.y) + floor(h.p.z);
-    tid = fmod(s, 2.0) == 0.0 ? t.even : t.odd;
+    tid = fmod(s, 2.0) == 0.0 ? th.z : th.y;
+    th = tex_head(S, tid);
   }
   return tid;
 }
@@ -1175,21 +1207,33 @@ RPK_INLINE uint32_t tex_resolve(const KScene& S, uint32_t tid, const Surf& h) {
 RPK_INLINE uint32_t texel(const KScene& S, uint64_t i) { return S.texels[i]; }
 
 // texture.rs:40-49 Image: clamp, then saturating `as u32` -> texel index
-RPK_INLINE uint64_t image_texel(const rpl::Texture& t, const Surf& h) {
-  const double w = (double)t.width, hh = (double)t.height;
+RPK_INLINE uint64_t image_texel(uint32_t width, uint32_t height, uint64_t texel_offset, const Surf& h) {
+  const double w = (double)width, hh = (double)height;
   double x = h.u * w, y = h.v * hh;
   if (x < 0.0) x = 0.0;
   if (x > w - 1.0) x = w - 1.0;
   if (y < 0.0) y = 0.0;
   if (y > hh - 1.0) y = hh - 1.0;
-  return t.texel_offset + (uint64_t)sat_u32(x) + (uint64_t)sat_u32(y) * t.width;
+  return texel_offset + (uint64_t)sat_u32(x) + (uint64_t)sat_u32(y) * width;
 }
 
-// texture.rs:21-118 value of a resolved (non-Checker) texture; `px` is the Image texel, fetched by the
-// caller ahead of use so its latency overlaps other shading work.
-RPK_INLINE V3 tex_value(const KScene& S, uint32_t tid, const Surf& h, uint32_t px) {
-  const rpl::Texture& t = S.texs[tid];
-  switch (t.kind) {
+// The texel of a resolved Image texture (width from its head): its height and offset are two more loads, issued
+// together, then the texel's.
+RPK_INLINE uint32_t image_fetch(const KScene& S, uint32_t tid, uint32_t width, const Surf& h) {
+  const uint32_t height = rec_load<uint32_t>(S.texs, tex_at(tid) + (uint32_t)offsetof(rpl::Texture, height));
+  const uint64_t off = rec_load<uint64_t>(S.texs, tex_at(tid) + (uint32_t)offsetof(rpl::Texture, texel_offset));
+  // (both count as read here, in the block that loads them: used only in the texel's block, one of them stays pending
+  // in the compiler's books on the paths around it, and the scatter's first write to its register waits for memory --
+  // for the texel too)
+  asm volatile("" : : "v"(height), "v"(off));
+  return texel(S, image_texel(width, height, off, h));
+}
+
+// texture.rs:21-118 value of a resolved (non-Checker) texture of kind `kind` (from its head: not read again);
+// `px` is the Image texel, fetched by the caller ahead of use so its latency overlaps other shading work.
+RPK_INLINE V3 tex_value(const KScene& S, uint32_t tid, uint32_t kind, const Surf& h, uint32_t px) {
+  const rpl::Texture& t = *reinterpret_cast<const rpl::Texture*>(reinterpret_cast<const char*>(S.texs) + tex_at(tid));
+  switch (kind) {
     case 1:  // DebugUVs
       return v3(h.u, h.v, 0.0);
     case 2:  // Solid
@@ -1233,10 +1277,10 @@ RPK_INLINE V3 tex_value(const KScene& S, uint32_t tid, const Surf& h, uint32_t p
 }
 
 RPK_INLINE V3 tex_sample(const KScene& S, uint32_t tid, const Surf& h) {
-  tid = tex_resolve(S, tid, h);
-  const rpl::Texture& t = S.texs[tid];
-  const uint32_t px = t.kind == 3 ? texel(S, image_texel(t, h)) : 0u;
-  return tex_value(S, tid, h, px);
+  uint4 th;
+  tid = tex_resolve(S, tid, h, th);
+  const uint32_t px = th.x == 3 ? image_fetch(S, tid, th.w, h) : 0u;
+  return tex_value(S, tid, th.x, h, px);
 }
 
 // material.rs:49-60 Emit::evaluate (SkySphere's texture value sampled by the caller)
@@ -1254,19 +1298,22 @@ RPK_INLINE V3 emit_eval(uint32_t kind, V3 color, V3 tex, V3 d, const Surf& h) {
 }
 
 // material.rs:74-81 Absorb::evaluate (AlbedoMap's texture value sampled by the caller)
-RPK_INLINE V3 absorb_eval(const rpl::Material& m, V3 tex) {
-  switch (m.absorb_kind) {
+RPK_INLINE V3 absorb_eval(uint32_t kind, V3 color, V3 tex) {
+  switch (kind) {
     case 1: return v3(1.0, 1.0, 1.0);
-    case 2: return v3(m.absorb_color[0], m.absorb_color[1], m.absorb_color[2]);
+    case 2: return color;
     case 3: return tex;
     default: return v3(0.0, 0.0, 0.0);
   }
 }
+RPK_INLINE V3 absorb_eval(const rpl::Material& m, V3 tex) {
+  return absorb_eval(m.absorb_kind, v3(m.absorb_color[0], m.absorb_color[1], m.absorb_color[2]), tex);
+}
 
 // material.rs:27-34, 115-179 Scatter::evaluate.  Returns true and the new direction when scattered.
 template <class R>
-RPK_INLINE bool scatter_eval(const rpl::Material& m, V3 d, const Surf& h, R& rng, V3& nd) {
-  switch (m.scatter_kind) {
+RPK_INLINE bool scatter_eval(uint32_t kind, double param, V3 d, const Surf& h, R& rng, V3& nd) {
+  switch (kind) {
     case 1: {  // Lambert (material.rs:115-130)
       DREG(DREG_LAMBERT)
       if (dot(h.n, d) > 0.0) return false;
@@ -1289,7 +1336,7 @@ RPK_INLINE bool scatter_eval(const rpl::Material& m, V3 d, const Surf& h, R& rng
         DREG(DREG_LOOP_METAL)
         if (ring_round<6u>(rng, a, q)) break;
       }
-      const V3 r = normalize(add(reflect(d, h.n), smul(m.scatter_param, v3(q.x, q.y, q.z))));
+      const V3 r = normalize(add(reflect(d, h.n), smul(param, v3(q.x, q.y, q.z))));
       if (dot(h.n, r) < 0.0) return false;
       nd = r;
       return true;
@@ -1298,8 +1345,8 @@ RPK_INLINE bool scatter_eval(const rpl::Material& m, V3 d, const Surf& h, R& rng
       DREG(DREG_DIELEC)
       double eta;
       V3 n;
-      if (dot(h.n, d) > 0.0) { eta = m.scatter_param; n = v3(-h.n.x, -h.n.y, -h.n.z); }
-      else { eta = 1.0 / m.scatter_param; n = h.n; }
+      if (dot(h.n, d) > 0.0) { eta = param; n = v3(-h.n.x, -h.n.y, -h.n.z); }
+      else { eta = 1.0 / param; n = h.n; }
       double r0 = (1.0 - eta) / (1.0 + eta);
       r0 = r0 * r0;                                  // powi(2)
       const double x = 1.0 + dot(n, d);
@@ -1332,13 +1379,22 @@ RPK_INLINE bool shade_ray(const KScene& S, const HitRec& hr, V3& o, V3& d, R& rn
                           D& sum_y, D& sum_z, bool first, U& hits) {
   const bool hit = hr.prim >= 0;
   Surf h;
-  const rpl::Material* m = nullptr;
+  // A hit's material: its head (the control words, rp_layout.h) and scatter_param, two loads that depend on the hit
+  // record alone and go out with the surface's first load, in front of shading's first wait.  Everything below
+  // branches on the head's bits; the record's f64 colours follow the scatter.
+  uint32_t moff = 0;
+  rpl::MaterialHead mh = rpl::material_head_unpack(0u, 0u);
+  double sparam = 0.0;
   bool sph_uv;
   if (hit) {
     DREG(DREG_SURF)
     DCYC_BEGIN(c0)
-    sph_uv = surface(S, hr, o, d, h);
-    m = &S.mats[h.material];
+    h.material = hit_material(S, hr);
+    moff = mat_at(h.material);
+    const uint2 hw = rec_load<uint2>(S.mats, moff + (uint32_t)offsetof(rpl::Material, head));
+    sparam = rec_load<double>(S.mats, moff + (uint32_t)offsetof(rpl::Material, scatter_param));
+    sph_uv = surface_at(S, hr, o, d, h, [&] { return (hw.x & rpl::MH_NEEDS_UV) != 0; });
+    mh = rpl::material_head_unpack(hw.x, hw.y);
     DCYC_END(DCYC_SURF, c0)
   } else {
     DREG(DREG_MISS)
@@ -1361,27 +1417,33 @@ RPK_INLINE bool shade_ray(const KScene& S, const HitRec& hr, V3& o, V3& d, R& rn
   // Textures: each lane reads at most one here -- the absorb map of a hit or the sky sphere of a miss
   // (or of an emissive hit); its Checker walk and Image texel load are issued BEFORE the scatter so
   // the load latency overlaps it.  A hit reading both takes the second in a rare extra pass.
-  const uint32_t emit_kind = hit ? m->emit_kind : S.background.kind;
-  const uint32_t emit_tex = hit ? m->emit_tex : S.background.tex;
-  const bool ta = hit && m->absorb_kind == 3, te = emit_kind == 4;
+  const uint32_t emit_kind = hit ? mh.emit_kind : S.background.kind;
+  uint32_t absorb_tex = mh.absorb_tex, emit_tex = hit ? mh.emit_tex : S.background.tex;
+  if (mh.wide) {  // texture ids beyond 16 bits: the head holds none
+    absorb_tex = rec_load<uint32_t>(S.mats, moff + (uint32_t)offsetof(rpl::Material, absorb_tex));
+    emit_tex = rec_load<uint32_t>(S.mats, moff + (uint32_t)offsetof(rpl::Material, emit_tex));
+  }
+  const bool ta = hit && mh.absorb_kind == 3, te = emit_kind == 4;
   const bool t1 = ta || te;
-  uint32_t tid1 = 0, px1 = 0;
+  uint32_t tid1 = 0, px1 = 0, kind1 = 0;
   // a miss under an Image sky sphere: size and offset are kernel arguments (scalar registers), so the
   // texel load waits on no texture-table load
   const bool sky_img = !hit && S.background.img_w != 0;
+  // Every load issued so far has been waited for by now on every path (the surface's own wait is a full one), but the
+  // compiler's books still hold one as pending and put a full wait in front of the scatter, behind the texel's load:
+  // the same wait here, where nothing is in flight, clears the books, and the texel then waits with the scatter's first
+  // ring window.
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
   DCYC_BEGIN(c2)
   if (t1) {
     if (sky_img) {
-      rpl::Texture t;
-      t.width = S.background.img_w;
-      t.height = S.background.img_h;
-      t.texel_offset = S.background.img_off;
       tid1 = S.background.tex;
-      px1 = texel(S, image_texel(t, h));
+      px1 = texel(S, image_texel(S.background.img_w, S.background.img_h, S.background.img_off, h));
     } else {
-      tid1 = tex_resolve(S, ta ? m->absorb_tex : emit_tex, h);
-      const rpl::Texture& t = S.texs[tid1];
-      if (t.kind == 3) px1 = texel(S, image_texel(t, h));
+      uint4 th;
+      tid1 = tex_resolve(S, ta ? absorb_tex : emit_tex, h, th);
+      kind1 = th.x;
+      if (kind1 == 3) px1 = image_fetch(S, tid1, th.w, h);
     }
   }
   DCYC_END(DCYC_TEXISSUE, c2)
@@ -1390,7 +1452,7 @@ RPK_INLINE bool shade_ray(const KScene& S, const HitRec& hr, V3& o, V3& d, R& rn
   bool scattered = false;
   if (hit) {
     DCYC_BEGIN(c3)
-    scattered = scatter_eval(*m, d, h, rng, nd);
+    scattered = scatter_eval(mh.scatter_kind, sparam, d, h, rng, nd);
     DCYC_END(DCYC_SCATTER, c3)
   }
   V3 tex_ab = v3(0.0, 0.0, 0.0), tex_em = v3(0.0, 0.0, 0.0);
@@ -1398,15 +1460,27 @@ RPK_INLINE bool shade_ray(const KScene& S, const HitRec& hr, V3& o, V3& d, R& rn
   if (t1) {
     DREG(DREG_TEX)
     const V3 tv = sky_img ? v3(u8_unit(px1 & 0xffu), u8_unit((px1 >> 8) & 0xffu), u8_unit((px1 >> 16) & 0xffu))
-                          : tex_value(S, tid1, h, px1);
+                          : tex_value(S, tid1, kind1, h, px1);
     if (ta) tex_ab = tv;
     else tex_em = tv;
   }
   if (ta && te) tex_em = tex_sample(S, emit_tex, h);
   DCYC_END(DCYC_TEXVAL, c4)
   DCYC_BEGIN(c5)
-  const double* ecol = hit ? m->emit_color : S.background.color;
-  const V3 em = emit_eval(emit_kind, v3(ecol[0], ecol[1], ecol[2]), tex_em, d, h);
+  // a hit's two colours (twelve registers, too many to hold across the scatter): four loads issued together and
+  // waited for once -- counted as read here, or the compiler moves each into the branch that reads it, behind a wait
+  // of its own
+  V3 acol = v3(0.0, 0.0, 0.0), ecol = v3(S.background.color[0], S.background.color[1], S.background.color[2]);
+  if (hit) {
+    constexpr uint32_t A = (uint32_t)offsetof(rpl::Material, absorb_color), E = (uint32_t)offsetof(rpl::Material, emit_color);
+    static_assert(A % 16 == 8 && E == A + 24, "absorb_color[1..2] and emit_color[0..1] as 16 B loads");
+    const double a0 = rec_load<double>(S.mats, moff + A), e2 = rec_load<double>(S.mats, moff + E + 16);
+    const double2 a12 = rec_load<double2>(S.mats, moff + A + 8), e01 = rec_load<double2>(S.mats, moff + E);
+    asm volatile("" : : "v"(a0), "v"(a12.x), "v"(a12.y), "v"(e01.x), "v"(e01.y), "v"(e2));
+    acol = v3(a0, a12.x, a12.y);
+    ecol = v3(e01.x, e01.y, e2);
+  }
+  const V3 em = emit_eval(emit_kind, ecol, tex_em, d, h);
   // emit + absorb (*) trace_path_continue (render.rs:108-115, 135-142), accumulated forward: each
   // bounce's T (*) emit goes straight into the pixel sum (main.rs:80 adds the sample's total; the
   // association differs in the last ulp only)
@@ -1415,7 +1489,7 @@ RPK_INLINE bool shade_ray(const KScene& S, const HitRec& hr, V3& o, V3& d, R& rn
   sum_z = sum_z + T_z * em.z;
   if (hit && first) hits++;
   if (scattered) {
-    const V3 ab = absorb_eval(*m, tex_ab);
+    const V3 ab = absorb_eval(mh.absorb_kind, acol, tex_ab);
     T_x = T_x * ab.x;
     T_y = T_y * ab.y;
     T_z = T_z * ab.z;

@@ -747,6 +747,38 @@ int rph_bvh_tree_hash_opt(const rp_scene_desc* desc, uint32_t node_format, uint3
   return RP_OK;
 }
 
+int rph_material_head(const uint32_t fields[6], uint32_t packed[2], uint32_t unpacked[7]) {
+  if (!fields || !packed || !unpacked) return fail("rph_material_head: non-NULL pointers");
+  rpl::Material m{};
+  m.scatter_kind = fields[0]; m.absorb_kind = fields[1]; m.emit_kind = fields[2]; m.needs_uv = fields[3];
+  m.absorb_tex = fields[4]; m.emit_tex = fields[5];
+  rpl::material_head_pack(m, packed[0], packed[1]);
+  const rpl::MaterialHead h = rpl::material_head_unpack(packed[0], packed[1]);
+  const uint32_t u[7] = {h.scatter_kind, h.absorb_kind, h.emit_kind, h.needs_uv, h.absorb_tex, h.emit_tex, h.wide ? 1u : 0u};
+  for (int k = 0; k < 7; k++) unpacked[k] = u[k];
+  return RP_OK;
+}
+
+int rph_scene_materials(const rp_scene_desc* desc, uint64_t cap, uint32_t* words, uint64_t* n_materials) {
+  if (!desc || !n_materials || (cap && !words)) return fail("rph_scene_materials: non-NULL pointers");
+  std::string err;
+  int rc = rpb::validate(desc, err);
+  if (rc != RP_OK) return fail(err);
+  rpb::PackedScene ps;
+  rpb::BuildOptions bo;
+  bo.tables_only = true;
+  bo.vertex_tables = false;
+  rc = rpb::build(desc, bo, ps, err);
+  if (rc != RP_OK) return fail(err);
+  *n_materials = desc->n_materials;
+  for (uint64_t i = 0; i < desc->n_materials && i < cap; i++) {
+    const rpl::Material& m = ps.materials[i];
+    const uint32_t w[8] = {m.scatter_kind, m.absorb_kind, m.emit_kind, m.absorb_tex, m.emit_tex, m.needs_uv, m.head, m.head_tex};
+    for (int k = 0; k < 8; k++) words[8 * i + k] = w[k];
+  }
+  return RP_OK;
+}
+
 namespace {
 inline uint32_t rotl32(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
 // ChaCha12 block `ctr` of `key` (randomness.rs:5 StdRng = rand_chacha 0.3 ChaCha12Rng).

@@ -8,6 +8,7 @@
 // order with the triangle operands pre-subtracted exactly as hittable.rs:71-72 computes them.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rpl {
@@ -190,15 +191,42 @@ struct alignas(16) PrimRef {
 static_assert(sizeof(PrimRef) == 16, "PrimRef must be 16 B");
 
 // Material: rp_material flattened (material.rs:87-91).
+//
+// head, head_tex (offsets 24, 28: one 8 B load beside scatter_param) repeat the six control words for the render
+// kernel's shading, which reads them with one load per hit instead of six (rp_device.h shade_ray):
+//   head     : scatter_kind bits 0-3, absorb_kind bits 4-7, emit_kind bits 8-11, MH_NEEDS_UV, MH_WIDE_TEX
+//   head_tex : absorb_tex | emit_tex << 16 -- unless either id needs more than 16 bits: then MH_WIDE_TEX is set,
+//              head_tex is 0 and the reader takes both ids from the u32 fields.
+// The builder writes them where it fills the record (material_head_pack); every other reader keeps the u32 fields.
 struct alignas(16) Material {
   uint32_t scatter_kind, absorb_kind, emit_kind, absorb_tex;
-  uint32_t emit_tex, needs_uv, pad1, pad2;  // needs_uv: a texture this material samples reads hit.uv
+  uint32_t emit_tex, needs_uv, head, head_tex;  // needs_uv: a texture this material samples reads hit.uv
   double scatter_param;
   double absorb_color[3];
   double emit_color[3];
   double pad3;
 };
 static_assert(sizeof(Material) == 96, "Material must be 96 B");
+static_assert(offsetof(Material, head) == 24 && offsetof(Material, scatter_param) == 32 &&
+              offsetof(Material, absorb_color) == 40 && offsetof(Material, emit_color) == 64, "Material offsets");
+
+constexpr uint32_t MH_NEEDS_UV = 1u << 12, MH_WIDE_TEX = 1u << 13;
+struct MaterialHead {
+  uint32_t scatter_kind, absorb_kind, emit_kind, needs_uv;
+  uint32_t absorb_tex, emit_tex;  // meaningless when wide
+  bool wide;                      // the texture ids are in the record's u32 fields only
+};
+// The head of a record from its own fields (kinds below 16: the builder's validate() refuses larger ones).
+RPL_HD inline void material_head_pack(const Material& m, uint32_t& head, uint32_t& head_tex) {
+  const bool wide = (m.absorb_tex | m.emit_tex) > 0xFFFFu;
+  head = (m.scatter_kind & 15u) | (m.absorb_kind & 15u) << 4 | (m.emit_kind & 15u) << 8 |
+         (m.needs_uv ? MH_NEEDS_UV : 0u) | (wide ? MH_WIDE_TEX : 0u);
+  head_tex = wide ? 0u : m.absorb_tex | m.emit_tex << 16;
+}
+RPL_HD inline MaterialHead material_head_unpack(uint32_t head, uint32_t head_tex) {
+  return {head & 15u, (head >> 4) & 15u, (head >> 8) & 15u, (head & MH_NEEDS_UV) ? 1u : 0u,
+          head_tex & 0xFFFFu, head_tex >> 16, (head & MH_WIDE_TEX) != 0};
+}
 
 // Texture (texture.rs:10-18); Image texels live in one RGBA8 pool.
 struct alignas(16) Texture {

@@ -209,7 +209,7 @@ HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save",
                 "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
                 "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
-                "rph_tiles_unit_walk"]
+                "rph_tiles_unit_walk", "rph_material_head", "rph_scene_materials"]
 
 
 def rp_lib_path() -> str:
@@ -385,6 +385,8 @@ def host() -> ctypes.CDLL:
     lib.rph_plan_tiles_launch.argtypes = [c_uint32] * 12 + [c_uint64, POINTER(rph_launch_plan)]
     lib.rph_tiles_unit_walk.argtypes = [c_uint32] * 11 + [c_void_p, c_uint32, c_uint32, c_void_p, c_uint64,
                                         POINTER(c_uint64), c_void_p, c_void_p]
+    lib.rph_material_head.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.rph_scene_materials.argtypes = [POINTER(rp_scene_desc), c_uint64, c_void_p, POINTER(c_uint64)]
     _host = lib
     return lib
 
