@@ -687,6 +687,80 @@ int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, co
                                  uint32_t n_prior, uint32_t n_frames, const double* d_frames, uint64_t frame_stride,
                                  double* d_mean, double* d_m2, double* d_var, void* stream);
 
+/* Temporal reprojection: the accumulation state kept across a camera move -- the temporal half of SVGF
+ * (Schied et al. 2017).  rp_reproject_device carries the previous pose's running mean, m2 and per-pixel frame count to
+ * where its surfaces appear from the current pose, guided by the depth and normal buffers of rp_render_aov at both
+ * poses; rp_accum_frames_counts_device then folds the new pose's frames in with the frame number taken per pixel.  A
+ * disoccluded pixel starts over (count 0), the others continue what they had.
+ *   Buffers are full frames in frame order (pixel (i, j) at j*W + i, row 0 at the bottom, as rp_denoise_device's): depth
+ *   1 double per pixel, normal, mean and m2 3 doubles, count 1 uint32 (the frames folded into that pixel).  The pass runs
+ *   on the CURRENT device and knows nothing of scenes or shards.
+ *   Definition.  IEEE binary64, in the order written, without contraction; floor is exact and sqrt correctly rounded.
+ *   Per camera c, on the host: ty_c = tan(0.5*fov), tx_c = ty_c * aspect_ratio.  R = orientation, R[3*col + row];
+ *   R.v = ((R[0]*v.x + R[3]*v.y) + R[6]*v.z, ...), Rt.v = ((R[0]*v.x + R[1]*v.y) + R[2]*v.z, ...), Rt taken as R's
+ *   inverse (lookat builds orthonormal columns).  Dot products and squared lengths are summed (x + y) + z.  For the
+ *   current pixel (i, j) with depth z_cur, normal n_cur, nn_cur = n_cur.n_cur:
+ *     1. u = ((double)i + 0.5) / W, v = ((double)j + 0.5) / H; sx = (2.0*u - 1.0) * tx_cur, sy = (2.0*v - 1.0) * ty_cur;
+ *        l = sqrt((sx*sx + sy*sy) + 1.0).
+ *     2. The pixel is geometry iff nn_cur > 0 and z_cur > 0, else sky.
+ *     3. Geometry: g = z_cur / l, L = (sx*g, sy*g, -g), D = R_cur.L, E = (D + pos_cur) - pos_prev per component.
+ *        Sky: L = (sx, sy, -1.0), E = R_cur.L (the background is at infinity: no translation).
+ *     4. q = Rt_prev.E, m = -q.z; fx = ((q.x / (m*tx_prev) + 1.0) * 0.5) * W - 0.5, fy likewise with q.y, ty_prev, H.
+ *     5. The pixel is off unless m > 0 and fx > -1.0 and fx < W and fy > -1.0 and fy < H (a NaN is off).
+ *     6. i0 = floor(fx), a = fx - i0; j0 = floor(fy), b = fy - j0; geometry: z_exp = sqrt(q.q).
+ *     7. Taps dy = 0, 1 (outer), dx = 0, 1 (inner): t = (i0 + dx, j0 + dy), w = (dx ? a : 1.0 - a) * (dy ? b : 1.0 - b).
+ *        A tap counts iff it lies inside the frame, w > 0, count_prev[t] >= 1 and its class matches -- sky: nn_t == 0;
+ *        geometry: nn_t > 0, and with d = z_t - z_exp, (d < 0 ? -d : d) <= sigma_depth * z_exp, and with c = n_cur.n_t,
+ *        c > 0 and c*c >= (normal_cos*normal_cos) * (nn_cur*nn_t).
+ *     8. From 0.0, in tap order: sw += w; acc[ch] += w * mean_t[ch]; sacc[ch] += w * s_t[ch], s_t[ch] = count_t >= 2 ?
+ *        m2_t[ch] / (double)(count_t - 1) : 0.0 (the per-frame variance); the first tap with a strictly larger w than
+ *        all before it gives n_best = count_t.
+ *     9. No counting tap: count = 0, mean = m2 = 0.0.  Otherwise count = min(n_best, max_history), mean = acc / sw,
+ *        m2 = (sacc / sw) * (double)(count - 1): "count frames with this mean and this per-frame variance", which the
+ *        fold below continues.  NaN in a counting tap's state propagates; a tap that does not count is never read into
+ *        the sums.
+ *   A zero field of rp_reproject_params takes its default: sigma_depth 0.05 (> 0, finite), normal_cos 0.9 (in (0, 1]),
+ *   max_history 32 (1 .. 2^31 - 1); params = NULL means all three.
+ *   d_stats (RP_REPROJECT_STATS_LEN uint64, 8-byte aligned) is zeroed on `stream`, then receives
+ *     [0] the pixels   [1] the pixels with count >= 1   [2] the sum of the counts   [3] the off pixels
+ *   -- order-free integer sums, exact and the same on every run.
+ * rp_reproject_device: asynchronous on `stream`, two launches, no allocation and no synchronisation (capturable).
+ * rp_reproject: the same on host buffers through the kernel on `device`, synchronous; *seconds (nullable) the device time.
+ * RP_EINVAL: a NULL pointer; a zero size or a side above 65535; parameters out of range; a camera field that is not
+ * finite or a fov with tan(0.5*fov) <= 0; an output aliasing an input or another output (a gather: in place is wrong). */
+#define RP_REPROJECT_STATS_LEN 4
+typedef struct rp_reproject_params {
+  double sigma_depth, normal_cos;
+  uint32_t max_history, reserved;
+} rp_reproject_params;
+int rp_reproject_params_init(rp_reproject_params* params);
+int rp_reproject_device(const rp_reproject_params* params, uint32_t width, uint32_t height, const rp_camera* cur,
+                        const rp_camera* prev, const double* d_depth_cur, const double* d_normal_cur,
+                        const double* d_depth_prev, const double* d_normal_prev, const double* d_mean_prev,
+                        const double* d_m2_prev, const uint32_t* d_count_prev, double* d_mean, double* d_m2,
+                        uint32_t* d_count, uint64_t* d_stats, void* stream);
+int rp_reproject(const rp_reproject_params* params, int device, uint32_t width, uint32_t height, const rp_camera* cur,
+                 const rp_camera* prev, const double* depth_cur, const double* normal_cur, const double* depth_prev,
+                 const double* normal_prev, const double* mean_prev, const double* m2_prev, const uint32_t* count_prev,
+                 double* mean, double* m2, uint32_t* count, uint64_t* stats, double* seconds);
+
+/* rp_accum_frames_counts_device: rp_accum_frames_device with the frame number taken per pixel.  Word w of pixel p of
+ * frame f sits at d_frames[f*frame_stride + p*words_per_pixel + w]; the state words of pixel p at p*words_per_pixel + w
+ * of d_mean and d_m2.  For pixel p with c = d_count[p], frames f = 0 .. n_frames - 1 are folded with k = c + f + 1,
+ * r = 1.0 / (double)k, by the Welford lines above, unchanged; with c == 0 the state is not read and starts at 0.0.
+ * Afterwards d_count[p] = c + n_frames.  d_var (nullable): with n = c + n_frames, m2 / ((double)n * (double)(n - 1)) for
+ * n >= 2, else var_one -- the caller's stand-in for "one frame, spread unknown", finite and >= 0 (a non-finite one would
+ * put 0 * inf into the variance-guided filter).  The caller keeps every count below 2^31 - n_frames (max_history does
+ * that for reprojected state).
+ *   Defined property: with every count equal to c, mean, m2 and (n >= 2) var equal rp_accum_frames_device's with
+ *   n_prior = c bit for bit.
+ * Asynchronous on `stream` on the CURRENT device; one launch, no allocation, no synchronisation.  RP_EINVAL: as
+ * rp_accum_frames_device (n_pixels*words_per_pixel for n_words), and words_per_pixel of zero, a NULL d_count, a var_one
+ * that is negative or not finite, d_count aliasing the frames or the state. */
+int rp_accum_frames_counts_device(uint64_t n_pixels, uint32_t words_per_pixel, uint32_t n_frames, const double* d_frames,
+                                  uint64_t frame_stride, uint32_t* d_count, double* d_mean, double* d_m2, double* d_var,
+                                  double var_one, void* stream);
+
 /* Output stage on the device: the reference's to_srgb_u8 (utility.rs:212-220, alpha 255) of every slot of
  * a compact shard buffer, bytes in tga::save's pixel order B, G, R, A (image.rs:116-137), so a gathered
  * and de-interleaved frame is the body of the reference's output.tga (18-byte header: rph_tga_save).

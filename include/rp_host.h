@@ -220,6 +220,16 @@ int rph_accum_tiles_select(const rp_render_params* params, const rp_error_params
                            const double* mean, const double* var, const uint32_t* tiles_in, uint32_t n_in, uint32_t* over,
                            uint32_t* tiles_out, uint32_t* count);
 
+/* Temporal reprojection on the CPU (include/rp.h rp_reproject_device and rp_accum_frames_counts_device: the
+ * definitions): plain loops over raytracing-potato_amd/csrc/rp_reproject.h and rp_accum.h, the headers the device
+ * kernels compile, so the two agree bit for bit.  Host buffers, the device calls' arguments and RP_EINVAL cases. */
+int rph_reproject(const rp_reproject_params* params, uint32_t width, uint32_t height, const rp_camera* cur,
+                  const rp_camera* prev, const double* depth_cur, const double* normal_cur, const double* depth_prev,
+                  const double* normal_prev, const double* mean_prev, const double* m2_prev, const uint32_t* count_prev,
+                  double* mean, double* m2, uint32_t* count, uint64_t* stats);
+int rph_accum_frames_counts(uint64_t n_pixels, uint32_t words_per_pixel, uint32_t n_frames, const double* frames,
+                            uint64_t frame_stride, uint32_t* count, double* mean, double* m2, double* var, double var_one);
+
 /* Test hooks: what rp_render_tiles_device_ws launches with (raytracing-potato_amd/csrc/rp_schedule.h
  * rps::plan_tiles_launch, the header librp.so's rp_tiles.hip calls), in the pattern of rph_plan_launch and rph_unit_walk
  * for a whole-frame params given field by field (shard 0 of 1, interleave).  rph_plan_tiles_launch fills the

@@ -1,7 +1,7 @@
 // rp_accum.hip -- progressive accumulation (include/rp.h rp_accum_frames_device and rp_accum_error_device_ws,
 // DESIGN.md 4.13): the frames of multi-frame launches folded into a running mean and the variance of that mean, and the
 // count of pixels whose relative standard error is still above a tolerance.  No ray is traced.  The arithmetic is
-// rp_accum.h's, shared with the CPU loops behind rph_accum_frames and rph_accum_error; this file is the two kernels,
+// rp_accum.h's, shared with the CPU loops behind rph_accum_frames and rph_accum_error; this file is the kernels,
 // their launches and the C-ABI.
 //
 // A translation unit of its own, linked into librp.so and librp_diag.so and, like rp_aov.hip, rp_denoise.hip and
@@ -14,6 +14,9 @@
 // accum_tiles_kernel (rp_accum_frames_tiles_device): the same per-lane body with a block indirection --
 // the words of listed block k of every frame folded into state block tiles[k], an entry at or above the state's block
 // count skipped; the wide path needs an even block size as well, so that every block starts on an even word.
+// accum_counts_kernel (rp_accum_frames_counts_device): the fold with the frame number taken per pixel --
+// a lane owns one pixel, reads its count c once, folds its words with k = c + 1 .., one division per frame, and writes
+// c + n_frames back; three words per pixel (rgb) and one are unrolled, any other number walks word by word.
 // error_kernel: a lane per shard slot, several slots per lane above 2048 blocks (rp_units.h slot_pixel's decode, as
 // rp_variance.hip); the four statistics are
 // reduced in the wave, then in the block through LDS, then one vector atomic per block and statistic -- integer sums and
@@ -141,6 +144,53 @@ __global__ void __launch_bounds__(ACC_BLOCK) accum_tiles_kernel(const TileArgs T
     fold<1>(T.A, src, dst);
     if (w + 1 < tw) fold<1>(T.A, src + 1, dst + 1);
   }
+}
+
+// The per-pixel fold (rp_accum_frames_counts_device).  A pixel's state is not read when its count is zero.
+struct CountArgs {
+  uint64_t n_pixels, stride;
+  uint32_t wpp, n_frames;
+  const double* frames;
+  uint32_t* count;
+  double* mean;
+  double* m2;
+  double* var;  // NULL: not wanted
+  double var_one;
+};
+
+// Words w0 .. w0 + W - 1 of the lane's pixel: frames outermost, so 1 / k is made once per frame for the W words.
+template <int W>
+__device__ __forceinline__ void fold_counts(const CountArgs& A, uint64_t w0, uint32_t c) {
+  double mean[W], m2[W];
+#pragma unroll
+  for (int i = 0; i < W; i++) mean[i] = c ? A.mean[w0 + i] : 0.0, m2[i] = c ? A.m2[w0 + i] : 0.0;
+  uint32_t k = c;
+  for (uint32_t f = 0; f < A.n_frames; f++) {
+    const double* x = A.frames + (uint64_t)f * A.stride + w0;
+    const double r = frame_weight(++k);
+#pragma unroll
+    for (int i = 0; i < W; i++) welford(x[i], r, mean[i], m2[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < W; i++) A.mean[w0 + i] = mean[i], A.m2[w0 + i] = m2[i];
+  if (A.var) {
+    const double nn = mean_divisor(k);
+#pragma unroll
+    for (int i = 0; i < W; i++) A.var[w0 + i] = k >= 2 ? mean_variance(m2[i], nn) : A.var_one;
+  }
+}
+
+__global__ void __launch_bounds__(ACC_BLOCK) accum_counts_kernel(const CountArgs A) {
+  const uint64_t p = (uint64_t)blockIdx.x * ACC_BLOCK + threadIdx.x;
+  if (p >= A.n_pixels) return;
+  const uint32_t c = A.count[p];
+  const uint64_t w0 = p * A.wpp;
+  if (A.wpp == 3) {
+    fold_counts<3>(A, w0, c);
+  } else {
+    for (uint32_t i = 0; i < A.wpp; i++) fold_counts<1>(A, w0 + i, c);
+  }
+  A.count[p] = c + A.n_frames;
 }
 
 struct ErrArgs {
@@ -286,6 +336,43 @@ int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, co
   const uint64_t lanes = t.lanes_per_tile * n_listed, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
   if (grid > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 blocks");
   hipLaunchKernelGGL(rpa::accum_tiles_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, t);
+  RP_HIP(hipGetLastError());
+  return RP_OK;
+}
+
+int rp_accum_frames_counts_device(uint64_t n_pixels, uint32_t words_per_pixel, uint32_t n_frames, const double* d_frames,
+                                  uint64_t frame_stride, uint32_t* d_count, double* d_mean, double* d_m2, double* d_var,
+                                  double var_one, void* stream) {
+  using rpp::overlaps;
+  if (!d_frames || !d_mean || !d_m2 || !d_count)
+    return fail(RP_EINVAL, "d_frames, d_count, d_mean and d_m2 must be non-NULL");
+  if (n_pixels == 0 || words_per_pixel == 0) return fail(RP_EINVAL, "n_pixels or words_per_pixel is zero");
+  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
+  if (n_frames > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames");
+  if (n_pixels > ((1ull << 40) - 512) / words_per_pixel)
+    return fail(RP_EINVAL, "n_pixels * words_per_pixel is above 2^40 - 512");
+  const uint64_t n_words = n_pixels * words_per_pixel;
+  if (frame_stride < n_words) return fail(RP_EINVAL, "frame_stride is below n_pixels * words_per_pixel: the frames would overlap");
+  if (!(var_one >= 0.0 && rpa::finite(var_one))) return fail(RP_EINVAL, "var_one must be finite and >= 0");
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_words;
+  const uint64_t count_bytes = 4 * n_pixels;
+  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
+    if (overlaps(o, out_bytes, d_frames, in_bytes))
+      return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias the frames");
+  if (overlaps(d_mean, out_bytes, d_m2, out_bytes) || overlaps(d_var, out_bytes, d_mean, out_bytes) ||
+      overlaps(d_var, out_bytes, d_m2, out_bytes))
+    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
+  if (overlaps(d_count, count_bytes, d_frames, in_bytes) || overlaps(d_count, count_bytes, d_mean, out_bytes) ||
+      overlaps(d_count, count_bytes, d_m2, out_bytes) || overlaps(d_count, count_bytes, d_var, out_bytes))
+    return fail(RP_EINVAL, "d_count must not alias the frames or the state");
+  const uint64_t grid = (n_pixels + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;  // < 2^32: n_pixels is below 2^40
+  if (grid > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 blocks");
+  rpa::CountArgs a;
+  a.n_pixels = n_pixels, a.stride = frame_stride;
+  a.wpp = words_per_pixel, a.n_frames = n_frames;
+  a.frames = d_frames, a.count = d_count, a.mean = d_mean, a.m2 = d_m2, a.var = d_var;
+  a.var_one = var_one;
+  hipLaunchKernelGGL(rpa::accum_counts_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, a);
   RP_HIP(hipGetLastError());
   return RP_OK;
 }

@@ -20,6 +20,7 @@
 #include "rp_isect.h"
 #include "rp_kernel.h"
 #include "rp_ray.h"
+#include "rp_reproject.h"
 #include "rp_schedule.h"
 #include "rp_units.h"
 
@@ -1316,6 +1317,91 @@ int rph_accum_tiles_select(const rp_render_params* params, const rp_error_params
       tiles_out[n_out++] = tile;
   }
   count[0] = n_out;
+  return RP_OK;
+}
+
+// rp_reproject.h's reproject_pixel per pixel and the four order-free statistics: what rp_reproject.hip's kernel does
+// per lane and reduces.
+int rph_reproject(const rp_reproject_params* params, uint32_t width, uint32_t height, const rp_camera* cur,
+                  const rp_camera* prev, const double* depth_cur, const double* normal_cur, const double* depth_prev,
+                  const double* normal_prev, const double* mean_prev, const double* m2_prev, const uint32_t* count_prev,
+                  double* mean, double* m2, uint32_t* count, uint64_t* stats) {
+  if (!cur || !prev) return fail("rph_reproject: cur and prev must be non-NULL");
+  if (const char* why = rprj::check_buffers(width, height, depth_cur, normal_cur, depth_prev, normal_prev, mean_prev,
+                                            m2_prev, count_prev, mean, m2, count, stats))
+    return fail(std::string("rph_reproject: ") + why);
+  rprj::Frame F;
+  if (!rprj::resolve(params, F.P))
+    return fail("rph_reproject: params out of range (sigma_depth > 0 and finite, normal_cos in (0, 1], max_history "
+                "1 .. 2^31 - 1)");
+  if (!rprj::make_camera(*cur, F.cur) || !rprj::make_camera(*prev, F.prev))
+    return fail("rph_reproject: a camera field is not finite, or tan(fov / 2) is not > 0");
+  F.W = width, F.H = height;
+  F.depth_prev = depth_prev, F.normal_prev = normal_prev;
+  F.mean_prev = mean_prev, F.m2_prev = m2_prev, F.count_prev = count_prev;
+  for (int k = 0; k < rprj::STATS_LEN; k++) stats[k] = 0;
+  for (uint32_t j = 0; j < height; j++)
+    for (uint32_t i = 0; i < width; i++) {
+      const uint64_t px = (uint64_t)j * width + i;
+      const rprj::Result r = rprj::reproject_pixel(F, i, j, depth_cur[px], normal_cur[3 * px], normal_cur[3 * px + 1],
+                                                   normal_cur[3 * px + 2]);
+      for (int ch = 0; ch < 3; ch++) mean[3 * px + ch] = r.mean[ch], m2[3 * px + ch] = r.m2[ch];
+      count[px] = r.count;
+      stats[rprj::STAT_PIXELS]++;
+      stats[rprj::STAT_KEPT] += r.count >= 1;
+      stats[rprj::STAT_COUNT] += r.count;
+      stats[rprj::STAT_OFF] += r.off;
+    }
+  return RP_OK;
+}
+
+// rp_accum.h's Welford update with the frame number taken per pixel: what rp_accum.hip's accum_counts_kernel does per
+// lane.
+int rph_accum_frames_counts(uint64_t n_pixels, uint32_t words_per_pixel, uint32_t n_frames, const double* frames,
+                            uint64_t frame_stride, uint32_t* count, double* mean, double* m2, double* var, double var_one) {
+  if (!frames || !mean || !m2 || !count)
+    return fail("rph_accum_frames_counts: frames, count, mean and m2 must be non-NULL");
+  if (n_pixels == 0 || words_per_pixel == 0) return fail("rph_accum_frames_counts: n_pixels or words_per_pixel is zero");
+  if (n_frames == 0) return fail("rph_accum_frames_counts: n_frames is zero: nothing to fold in");
+  if (n_frames > 0x7fffffffu) return fail("rph_accum_frames_counts: more than 2^31 - 1 frames");
+  if (n_pixels > ((1ull << 40) - 512) / words_per_pixel)
+    return fail("rph_accum_frames_counts: n_pixels * words_per_pixel is above 2^40 - 512");
+  const uint64_t n_words = n_pixels * words_per_pixel;
+  if (frame_stride < n_words)
+    return fail("rph_accum_frames_counts: frame_stride is below n_pixels * words_per_pixel: the frames would overlap");
+  if (!(var_one >= 0.0 && rpa::finite(var_one))) return fail("rph_accum_frames_counts: var_one must be finite and >= 0");
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_words;
+  auto overlaps = [](const void* a, uint64_t na, const void* b, uint64_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+  };
+  if (overlaps(mean, out_bytes, frames, in_bytes) || overlaps(m2, out_bytes, frames, in_bytes) ||
+      overlaps(var, out_bytes, frames, in_bytes))
+    return fail("rph_accum_frames_counts: mean, m2 and var must not alias the frames");
+  if (overlaps(mean, out_bytes, m2, out_bytes) || overlaps(var, out_bytes, mean, out_bytes) ||
+      overlaps(var, out_bytes, m2, out_bytes))
+    return fail("rph_accum_frames_counts: mean, m2 and var must not alias one another");
+  if (overlaps(count, 4 * n_pixels, frames, in_bytes) || overlaps(count, 4 * n_pixels, mean, out_bytes) ||
+      overlaps(count, 4 * n_pixels, m2, out_bytes) || overlaps(count, 4 * n_pixels, var, out_bytes))
+    return fail("rph_accum_frames_counts: count must not alias the frames or the state");
+  for (uint64_t p = 0; p < n_pixels; p++) {
+    const uint32_t c = count[p], n = c + n_frames;
+    double* mp = mean + p * words_per_pixel;
+    double* qp = m2 + p * words_per_pixel;
+    if (!c)
+      for (uint32_t w = 0; w < words_per_pixel; w++) mp[w] = 0.0, qp[w] = 0.0;
+    for (uint32_t f = 0; f < n_frames; f++) {
+      const double r = rpa::frame_weight(c + f + 1);
+      const double* x = frames + (uint64_t)f * frame_stride + p * words_per_pixel;
+      for (uint32_t w = 0; w < words_per_pixel; w++) rpa::welford(x[w], r, mp[w], qp[w]);
+    }
+    if (var) {
+      const double nn = rpa::mean_divisor(n);
+      for (uint32_t w = 0; w < words_per_pixel; w++)
+        var[p * words_per_pixel + w] = n >= 2 ? rpa::mean_variance(qp[w], nn) : var_one;
+    }
+    count[p] = n;
+  }
   return RP_OK;
 }
 

@@ -39,6 +39,7 @@ RP_STATUS_STACK_OVERFLOW, RP_STATUS_PLAN_MISMATCH = 1, 2
 RP_ABI_VERSION = 9
 RP_MAX_FRAMES = 64
 RP_ERROR_STATS_LEN = 4  # rp_accum_error_device_ws: pixels counted, pixels over, bits of the largest finite e2, non-finite
+RP_REPROJECT_STATS_LEN = 4  # rp_reproject_device: pixels, pixels with count >= 1, the sum of the counts, off pixels
 RP_FRAME_ORDER_AUTO, RP_FRAME_ORDER_SEQUENTIAL, RP_FRAME_ORDER_INTERLEAVED, RP_FRAME_ORDER_PIXEL = 0, 1, 2, 3
 
 
@@ -119,6 +120,10 @@ class rp_error_params(Structure):  # include/rp.h: a zero field takes its defaul
     _fields_ = [("tol", c_double), ("eps", c_double)]
 
 
+class rp_reproject_params(Structure):  # include/rp.h: a zero field takes its default (0.05, 0.9, 32)
+    _fields_ = [("sigma_depth", c_double), ("normal_cos", c_double), ("max_history", c_uint32), ("reserved", c_uint32)]
+
+
 class rph_mesh(Structure):
     _fields_ = [("n_vertices", c_uint32), ("n_indices", c_uint32), ("positions", POINTER(c_double)),
                 ("normals", POINTER(c_double)), ("uvs", POINTER(c_double)), ("indices", POINTER(c_uint32))]
@@ -194,7 +199,8 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_denoise_device", "rp_denoise", "rp_render_variance_device_ws", "rp_denoise_var_params_init",
               "rp_denoise_var_scratch_bytes", "rp_denoise_var_device", "rp_denoise_var", "rp_accum_frames_device",
               "rp_accum_error_device_ws", "rp_render_tiles_device_ws", "rp_accum_tiles_select_device",
-              "rp_accum_frames_tiles_device", "rp_scene_tree"]
+              "rp_accum_frames_tiles_device", "rp_scene_tree", "rp_reproject_params_init", "rp_reproject_device",
+              "rp_reproject", "rp_accum_frames_counts_device"]
 class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
     _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
                 ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
@@ -209,7 +215,8 @@ HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save",
                 "rph_stdrng_u64", "rph_make_div32", "rph_plan_launch", "rph_draw_round", "rph_ray_setup", "rph_prim_test",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
                 "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
-                "rph_tiles_unit_walk", "rph_material_head", "rph_scene_materials"]
+                "rph_tiles_unit_walk", "rph_material_head", "rph_scene_materials", "rph_reproject",
+                "rph_accum_frames_counts"]
 
 
 def rp_lib_path() -> str:
@@ -326,6 +333,13 @@ def rp() -> ctypes.CDLL:
                                                  c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.rp_scene_tree.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint32),
                                   POINTER(c_uint32)]
+    lib.rp_reproject_params_init.argtypes = [POINTER(rp_reproject_params)]
+    lib.rp_reproject_device.argtypes = [POINTER(rp_reproject_params), c_uint32, c_uint32, POINTER(rp_camera),
+                                        POINTER(rp_camera)] + [c_void_p] * 12
+    lib.rp_reproject.argtypes = [POINTER(rp_reproject_params), c_int, c_uint32, c_uint32, POINTER(rp_camera),
+                                 POINTER(rp_camera)] + [c_void_p] * 11 + [POINTER(c_double)]
+    lib.rp_accum_frames_counts_device.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_double, c_void_p]
     if lib.rp_abi_version() != RP_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rp_abi_version()}, bindings expect {RP_ABI_VERSION} (rebuild)")
     _rp = lib
@@ -387,6 +401,10 @@ def host() -> ctypes.CDLL:
                                         POINTER(c_uint64), c_void_p, c_void_p]
     lib.rph_material_head.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.rph_scene_materials.argtypes = [POINTER(rp_scene_desc), c_uint64, c_void_p, POINTER(c_uint64)]
+    lib.rph_reproject.argtypes = [POINTER(rp_reproject_params), c_uint32, c_uint32, POINTER(rp_camera),
+                                  POINTER(rp_camera)] + [c_void_p] * 11
+    lib.rph_accum_frames_counts.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_double]
     _host = lib
     return lib
 

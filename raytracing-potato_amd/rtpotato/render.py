@@ -473,6 +473,74 @@ class DeviceScene:
                        params=denoise, stream=s, variance=out["variance"])
         return out
 
+    # ---- a camera sequence with reprojected history (rp_reproject_device) ----------------------
+    def render_sequence(self, params: RenderParams, cameras, frames_per_pose: int = 2, max_history: int = 32,
+                        var_one: float = 1.0, reproject=None, denoise=None, stream=None):
+        """An animation that keeps its accumulated history across camera moves: a generator over `cameras` (Camera
+        objects), one dict per pose.  Pose t renders `frames_per_pose` frames (render_frames_device at
+        seed + t * frames_per_pose * B * W * H, B = ceil(spp / samples_per_stream), so no stream repeats) and the guides
+        (render_aov_device) at its camera, assembles them to frame order, carries pose t - 1's mean, m2 and per-pixel
+        frame count to the new pixels (reproject_device with reproject_prev_camera(pose t - 1's camera), so a tilted
+        lookat camera reprojects exactly; pose 0 starts from zero counts), folds the new frames in with
+        the frame number taken per pixel (accum_frames_counts_device; a pixel with one frame gets the variance
+        `var_one`) and, unless denoise is False, filters the mean with that variance (denoise_device(variance=...);
+        `denoise`: as denoise_var_params takes it).  reproject: as reproject_params takes it; max_history overrides
+        its field.  Everything runs on `stream` (torch stream; default: current) with no host synchronisation inside a
+        pose.  Yields {"mean", "variance": (h, w, 3) f64, "count": (h, w) int32, "denoised": (h, w, 3) f64 or None,
+        "stats": int64[RP_REPROJECT_STATS_LEN] (reproject_stats decodes them; pose 0: every pixel, nothing kept)},
+        torch tensors on the scene's device, valid once the stream has drained.  One device holds the whole frame."""
+        import torch
+        from dataclasses import replace
+        _whole_frame(params, "render_sequence")
+        if not 1 <= frames_per_pose <= F.RP_MAX_FRAMES:
+            raise ValueError(f"frames_per_pose must be 1..{F.RP_MAX_FRAMES}, got {frames_per_pose}")
+        if not 1 <= max_history < 2 ** 31:
+            raise ValueError(f"max_history must be 1 .. 2^31 - 1, got {max_history}")
+        rp = reproject_params(reproject, max_history=max_history)
+        dev = torch.device("cuda", self.device)
+        s = _stream(stream, dev)
+        w, h, n = params.width, params.height, shard_slot_count(params)
+        nbatch = -(-params.spp // (params.samples_per_stream or F.RP_SAMPLES_PER_STREAM))
+        self.reserve_frames(params, frames_per_pose)
+        f64 = {"dtype": torch.float64, "device": dev}
+        prev = None
+        for t, cam in enumerate(cameras):
+            with torch.cuda.stream(s):
+                q = replace(params, seed=(params.seed + t * frames_per_pose * nbatch * w * h) & 0xFFFFFFFFFFFFFFFF)
+                shard_frames = torch.empty(frames_per_pose * 3 * n, **f64)
+                ctr = torch.zeros(F.RP_COUNTERS_LEN, dtype=torch.int64, device=dev)
+                self.render_frames_device(q, frames_per_pose, shard_frames, ctr, camera=cam, stream=s)
+                shard = {k: torch.empty(c * n, **f64) for k, c in (("normal", 3), ("albedo", 3), ("depth", 1))}
+                self.render_aov_device(params, normal=shard["normal"], albedo=shard["albedo"], depth=shard["depth"],
+                                       camera=cam, stream=s)
+                cur = {"normal": torch.empty((h, w, 3), **f64), "albedo": torch.empty((h, w, 3), **f64),
+                       "depth": torch.empty((h, w), **f64), "camera": cam}
+                frames = torch.empty((frames_per_pose, h, w, 3), **f64)
+                _assemble(params, shard, cur, _stream_ptr(s))
+                _assemble(params, {f: shard_frames[f * 3 * n:(f + 1) * 3 * n] for f in range(frames_per_pose)}, frames,
+                          _stream_ptr(s))
+                cur.update(mean=torch.empty((h, w, 3), **f64), m2=torch.empty((h, w, 3), **f64))
+                var = torch.empty((h, w, 3), **f64)
+                stats = torch.zeros(F.RP_REPROJECT_STATS_LEN, dtype=torch.int64, device=dev)
+                if prev is None:
+                    cur["count"] = torch.zeros((h, w), dtype=torch.int32, device=dev)
+                    stats[:1].fill_(w * h)
+                else:
+                    cur["count"] = torch.empty((h, w), dtype=torch.int32, device=dev)
+                    reproject_device(cam, reproject_prev_camera(prev["camera"]), cur["depth"], cur["normal"],
+                                     prev["depth"], prev["normal"],
+                                     prev["mean"], prev["m2"], prev["count"], cur["mean"], cur["m2"], cur["count"],
+                                     stats, params=rp, stream=s)
+                accum_frames_counts_device(frames, frames_per_pose, cur["count"], cur["mean"], cur["m2"], var=var,
+                                           var_one=var_one, stream=s)
+                out = None
+                if denoise is not False:
+                    out = torch.empty((h, w, 3), **f64)
+                    denoise_device(cur["mean"], cur["normal"], cur["albedo"], cur["depth"], out, params=denoise,
+                                   stream=s, variance=var)
+                prev = cur
+            yield {"mean": cur["mean"], "variance": var, "count": cur["count"], "denoised": out, "stats": stats}
+
     # ---- tile-adaptive progressive rendering (rp_render_tiles_device_ws, rp_accum_tiles_*; DESIGN.md 4.14) ------
     def render_tiles_device(self, params: RenderParams, tiles, n_listed: int, n_frames: int, out, counters, fg=None,
                             camera=None, stream=None, workspace: "Workspace | None" = None, order="auto") -> None:
@@ -1069,6 +1137,166 @@ def accum_frames_tiles_host(frames, n_frames: int, tiles, n_listed: int, tile_wo
     F.check_host(F.host().rph_accum_frames_tiles(
         tile_words, n_state_tiles, tiles.ctypes.data if tiles.size else None, n_listed, n_prior, n_frames,
         frames.ctypes.data, stride, mean.ctypes.data, m2.ctypes.data, var.ctypes.data if var is not None else None))
+
+
+# ---- temporal reprojection (rp_reproject*, rp_accum_frames_counts_device, include/rp.h) ----
+def reproject_params(params=None, **kw) -> F.rp_reproject_params:
+    """rp_reproject_params: `params` (an rp_reproject_params, a dict of its fields or None) with fields overridden by
+    keyword.  Fields left at zero take the library's defaults (sigma_depth 0.05, normal_cos 0.9, max_history 32)."""
+    p = F.rp_reproject_params()
+    if isinstance(params, F.rp_reproject_params):
+        ctypes.memmove(ctypes.byref(p), ctypes.byref(params), ctypes.sizeof(p))
+    elif params:
+        kw = {**params, **kw}
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise KeyError(f"unknown reproject parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _camera_c(camera) -> F.rp_camera:
+    return camera if isinstance(camera, F.rp_camera) else camera.to_c()
+
+
+def reproject_prev_camera(camera) -> F.rp_camera:
+    """`camera` (Camera or rp_camera) as the `prev` argument of the reprojection calls: the same camera with its
+    orientation replaced by the inverse transpose, columns (c1 x c2, c2 x c0, c0 x c1) / det.  The pass takes the
+    transpose of prev's orientation for its inverse, which holds for orthonormal columns only, and
+    Transformation.lookat's x and y columns are shorter than 1 whenever the camera looks up or down (x = up x z is not
+    normalised); the transpose of what this returns IS the inverse, so the reprojection is exact for any camera.  An
+    orthonormal orientation comes back unchanged up to rounding."""
+    c = _camera_c(camera)
+    o = list(c.orientation)
+    col = [o[0:3], o[3:6], o[6:9]]
+
+    def cross(a, b):
+        return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+    dual = [cross(col[1], col[2]), cross(col[2], col[0]), cross(col[0], col[1])]
+    det = (col[0][0] * dual[0][0] + col[0][1] * dual[0][1]) + col[0][2] * dual[0][2]
+    if not det != 0.0:
+        raise ValueError("the camera's orientation is singular")
+    out = F.rp_camera()
+    ctypes.memmove(ctypes.byref(out), ctypes.byref(c), ctypes.sizeof(out))
+    out.orientation[:] = [x / det for v in dual for x in v]
+    return out
+
+
+def reproject_stats(stats) -> dict:
+    """The RP_REPROJECT_STATS_LEN words of a reprojection: pixels, those that kept history (count >= 1), the sum of the
+    counts and the pixels that fell off the previous frame."""
+    w = [int(x) for x in np.asarray(stats).reshape(-1)[:F.RP_REPROJECT_STATS_LEN]]
+    return {"pixels": w[0], "kept": w[1], "count_sum": w[2], "off": w[3]}
+
+
+def reproject_device(cur, prev, depth, normal, depth_prev, normal_prev, mean_prev, m2_prev, count_prev, mean, m2, count,
+                     stats, params=None, stream=None) -> None:
+    """rp_reproject_device on torch tensors of one device, asynchronously on `stream` (torch stream; default: current):
+    the state of the previous pose (mean_prev, m2_prev (h, w, 3) f64, count_prev (h, w) int32, frame order) carried to
+    the current pose's pixels into mean, m2, count, guided by both poses' depth (h, w) and normal (h, w, 3) from
+    render_aov; cur, prev: Camera or rp_camera -- prev as reproject_prev_camera gives it unless its orientation is
+    orthonormal.  stats: int64, RP_REPROJECT_STATS_LEN (reproject_stats decodes them).
+    The frame's size is `count`'s shape; no output may alias an input.  params: as reproject_params takes them."""
+    import torch
+    assert count.dtype == torch.int32 and count.is_cuda and count.is_contiguous() and count.dim() == 2
+    h, w = count.shape
+    dev = count.device
+    for t, dt, m in ((depth, torch.float64, w * h), (normal, torch.float64, 3 * w * h), (depth_prev, torch.float64, w * h),
+                     (normal_prev, torch.float64, 3 * w * h), (mean_prev, torch.float64, 3 * w * h),
+                     (m2_prev, torch.float64, 3 * w * h), (count_prev, torch.int32, w * h), (mean, torch.float64, 3 * w * h),
+                     (m2, torch.float64, 3 * w * h), (stats, torch.int64, F.RP_REPROJECT_STATS_LEN)):
+        _check_tensor(t, dt, m, device=dev)
+        assert t.numel() == m
+    p, cc, cp = reproject_params(params), _camera_c(cur), _camera_c(prev)
+    with torch.cuda.device(dev):
+        F.check(F.rp().rp_reproject_device(ctypes.byref(p), w, h, ctypes.byref(cc), ctypes.byref(cp), depth.data_ptr(),
+                                           normal.data_ptr(), depth_prev.data_ptr(), normal_prev.data_ptr(),
+                                           mean_prev.data_ptr(), m2_prev.data_ptr(), count_prev.data_ptr(),
+                                           mean.data_ptr(), m2.data_ptr(), count.data_ptr(), stats.data_ptr(),
+                                           _stream_ptr(stream, dev)))
+
+
+def _reproject_host_frames(depth, normal, depth_prev, normal_prev, mean_prev, m2_prev, count_prev):
+    depth = np.ascontiguousarray(depth, dtype=np.float64)
+    assert depth.ndim == 2, "depth: (h, w)"
+    h, w = depth.shape
+    f3 = [np.ascontiguousarray(a, dtype=np.float64) for a in (normal, normal_prev, mean_prev, m2_prev)]
+    depth_prev = np.ascontiguousarray(depth_prev, dtype=np.float64)
+    count_prev = np.ascontiguousarray(count_prev, dtype=np.uint32)
+    assert all(a.shape == (h, w, 3) for a in f3) and depth_prev.shape == (h, w) and count_prev.shape == (h, w)
+    out = (np.empty((h, w, 3)), np.empty((h, w, 3)), np.empty((h, w), dtype=np.uint32),
+           np.zeros(F.RP_REPROJECT_STATS_LEN, dtype=np.uint64))
+    ptrs = [a.ctypes.data for a in (depth, f3[0], depth_prev, f3[1], f3[2], f3[3], count_prev) + out]
+    return w, h, ptrs, out
+
+
+def reproject_host(cur, prev, depth, normal, depth_prev, normal_prev, mean_prev, m2_prev, count_prev, params=None) -> tuple:
+    """rph_reproject: the same pass on the CPU (librp_host.so; the same arithmetic header as the kernel, equal bits) on
+    numpy frames: (mean (h, w, 3), m2 (h, w, 3), count (h, w) uint32, stats uint64[RP_REPROJECT_STATS_LEN])."""
+    w, h, ptrs, out = _reproject_host_frames(depth, normal, depth_prev, normal_prev, mean_prev, m2_prev, count_prev)
+    p, cc, cp = reproject_params(params), _camera_c(cur), _camera_c(prev)
+    F.check_host(F.host().rph_reproject(ctypes.byref(p), w, h, ctypes.byref(cc), ctypes.byref(cp), *ptrs))
+    return out
+
+
+def reproject(cur, prev, depth, normal, depth_prev, normal_prev, mean_prev, m2_prev, count_prev, params=None,
+              device: int = 0) -> tuple:
+    """rp_reproject: reproject_host's arguments and results through the device kernel, and the device seconds."""
+    w, h, ptrs, out = _reproject_host_frames(depth, normal, depth_prev, normal_prev, mean_prev, m2_prev, count_prev)
+    p, cc, cp = reproject_params(params), _camera_c(cur), _camera_c(prev)
+    sec = ctypes.c_double()
+    F.check(F.rp().rp_reproject(ctypes.byref(p), device, w, h, ctypes.byref(cc), ctypes.byref(cp), *ptrs,
+                                ctypes.byref(sec)))
+    return out + (sec.value,)
+
+
+def _counts_shape(n_frames: int, n_pixels, wpp: int, stride, count_len: int, state_len: int, frames_len: int):
+    n_pixels = count_len if n_pixels is None else int(n_pixels)
+    stride = n_pixels * wpp if stride is None else int(stride)
+    # what the library would read and write must lie inside the buffers; its own refusals stay the library's
+    assert n_pixels <= count_len and n_pixels * wpp <= state_len, "count, mean, m2 and var: too short for n_pixels"
+    if n_frames >= 1 and stride >= n_pixels * wpp:
+        assert frames_len >= (n_frames - 1) * stride + n_pixels * wpp, "frames: (n_frames - 1) * stride + words"
+    return n_pixels, stride
+
+
+def accum_frames_counts_device(frames, n_frames: int, count, mean, m2, var=None, var_one: float = 1.0,
+                               words_per_pixel: int = 3, n_pixels=None, stride=None, stream=None) -> None:
+    """rp_accum_frames_counts_device on torch tensors of one device, asynchronously on `stream` (torch stream; default:
+    current): accum_frames_device with the frame number taken per pixel -- pixel p, which holds count[p] (int32) frames
+    already (0: its state is only written), folds its words_per_pixel words of the n_frames blocks of `frames` (block f
+    at f * stride; default n_pixels * words_per_pixel) and count[p] grows by n_frames; `var` (optional) receives the
+    variance of the mean, var_one where a pixel has one frame.  n_pixels default: count.numel()."""
+    import torch
+    for t in (frames, mean, m2, var):
+        if t is not None:
+            _check_tensor(t, torch.float64, 0, device=mean.device)
+    _check_tensor(count, torch.int32, 0, device=mean.device)
+    small = min(t.numel() for t in (mean, m2, var) if t is not None)
+    n_pixels, stride = _counts_shape(n_frames, n_pixels, words_per_pixel, stride, count.numel(), small, frames.numel())
+    with torch.cuda.device(mean.device):
+        F.check(F.rp().rp_accum_frames_counts_device(n_pixels, words_per_pixel, n_frames, frames.data_ptr(), stride,
+                                                     count.data_ptr(), mean.data_ptr(), m2.data_ptr(),
+                                                     var.data_ptr() if var is not None else None, var_one,
+                                                     _stream_ptr(stream, mean.device)))
+
+
+def accum_frames_counts_host(frames, n_frames: int, count, mean, m2, var=None, var_one: float = 1.0,
+                             words_per_pixel: int = 3, n_pixels=None, stride=None) -> None:
+    """rph_accum_frames_counts: the same fold on the CPU (librp_host.so; equal bits), in place on contiguous numpy
+    arrays (f64; count uint32)."""
+    for a in (frames, mean, m2, var):
+        if a is not None:
+            assert isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous
+    assert isinstance(count, np.ndarray) and count.dtype == np.uint32 and count.flags.c_contiguous
+    for a in (count, mean, m2, var):
+        assert a is None or a.flags.writeable
+    small = min(a.size for a in (mean, m2, var) if a is not None)
+    n_pixels, stride = _counts_shape(n_frames, n_pixels, words_per_pixel, stride, count.size, small, frames.size)
+    F.check_host(F.host().rph_accum_frames_counts(n_pixels, words_per_pixel, n_frames, frames.ctypes.data, stride,
+                                                  count.ctypes.data, mean.ctypes.data, m2.ctypes.data,
+                                                  var.ctypes.data if var is not None else None, var_one))
 
 
 def denoise_device(rgb, normal, albedo, depth, out, scratch=None, params=None, stream=None, variance=None) -> None:

@@ -7,6 +7,8 @@
 //     triangle soup, a mesh with shared vertices and degenerate (zero-area, duplicated) triangles, and spheres;
 //   - the CPU traversal model (rph_bvh_traversal_stats_ex) and the exact primitive tests (rph_prim_test) over random rays;
 //   - the render kernel's unit fetch in its host environment (rph_unit_walk: csrc/rp_units.h);
+//   - the passes' host loops on exactly sized buffers: denoisers, variance, accumulation, tile selection, and temporal
+//     reprojection with its per-pixel fold (rph_reproject, rph_accum_frames_counts);
 //   - the OBJ and TGA readers (mesh.rs:145-183, image.rs:73-114) on files this driver writes, including truncated and
 //     malformed ones (they must fail cleanly), and the TGA writer;
 //   - the bulk StdRng (rph_stdrng_u64, threaded) against the oracle's sequential stream;
@@ -450,12 +452,62 @@ static void check_tiles() {
               "a short state, a short stride, a full tile share, 16385 entries and a short unit buffer refused\n");
 }
 
+// temporal reprojection's host loops (csrc/rp_reproject.h rph_reproject; csrc/rp_accum.h rph_accum_frames_counts) on a
+// 9 x 7 frame with exactly sized buffers: a camera that steps sideways over a plane with two sky pixels and two pixels
+// without history, a previous camera that faces away (every pixel off), then the per-pixel fold of two frames
+static void check_reproject() {
+  const uint32_t W = 9, H = 7, n = W * H;
+  std::vector<double> dep(n), nrm(3 * n), mean0(3 * n), m20(3 * n), mean(3 * n), m2(3 * n), var(3 * n), fr(2 * 3 * n);
+  std::vector<uint32_t> cnt0(n), cnt(n);
+  for (uint32_t i = 0; i < n; i++) {
+    const bool sky = i == 5 || i == 40;
+    dep[i] = sky ? 0.0 : 4.0 + 0.01 * (i % W);
+    for (int k = 0; k < 3; k++) {
+      nrm[3 * i + k] = sky ? 0.0 : (k == 2 ? 1.0 : 0.05);
+      mean0[3 * i + k] = 0.2 + 0.01 * ((i * 5 + k) % 13);
+      m20[3 * i + k] = 0.001 * ((i + k) % 7);
+    }
+    cnt0[i] = i == 11 || i == 30 ? 0 : 1 + i % 40;  // some above max_history = 32
+  }
+  for (size_t i = 0; i < fr.size(); i++) fr[i] = 0.3 + 0.01 * (i % 17);
+  rp_camera cur{}, prev{};
+  cur.aspect_ratio = (double)W / H, cur.fov = 0.8, cur.focal_dist = 1.0;
+  cur.orientation[0] = cur.orientation[4] = cur.orientation[8] = 1.0;
+  cur.position[2] = 4.0;
+  prev = cur;
+  prev.position[0] = 0.6;  // 1.2 pixels at this depth: the first column leaves the previous frame
+  uint64_t st[RP_REPROJECT_STATS_LEN];
+  CHECK(rph_reproject(nullptr, W, H, &cur, &prev, dep.data(), nrm.data(), dep.data(), nrm.data(), mean0.data(), m20.data(),
+                      cnt0.data(), mean.data(), m2.data(), cnt.data(), st) == RP_OK);
+  CHECK(st[0] == n && st[1] > n / 2 && st[1] < n && st[2] >= st[1] && st[3] > 0 && st[3] < n);
+  for (uint32_t i = 0; i < n; i++) CHECK(cnt[i] <= 32 && (cnt[i] || (mean[3 * i] == 0.0 && m2[3 * i] == 0.0)));
+  CHECK(rph_accum_frames_counts(n, 3, 2, fr.data(), 3 * n, cnt.data(), mean.data(), m2.data(), var.data(), 0.5) == RP_OK);
+  for (uint32_t i = 0; i < n; i++) CHECK(cnt[i] >= 2 && cnt[i] <= 34 && var[3 * i] >= 0.0 && mean[3 * i] > 0.0);
+  prev.orientation[0] = prev.orientation[8] = -1.0;  // turned about y: the scene lies behind it
+  CHECK(rph_reproject(nullptr, W, H, &cur, &prev, dep.data(), nrm.data(), dep.data(), nrm.data(), mean0.data(), m20.data(),
+                      cnt0.data(), mean.data(), m2.data(), cnt.data(), st) == RP_OK);
+  CHECK(st[1] == 0 && st[2] == 0 && st[3] == n);
+  std::vector<uint32_t> one(n, 0);
+  CHECK(rph_accum_frames_counts(n, 3, 1, fr.data(), 3 * n, one.data(), mean.data(), m2.data(), var.data(), 0.5) == RP_OK);
+  for (uint32_t i = 0; i < 3 * n; i++) CHECK(mean[i] == fr[i] && m2[i] == 0.0 && var[i] == 0.5);
+  CHECK(rph_reproject(nullptr, W, H, &cur, &prev, dep.data(), nrm.data(), dep.data(), nrm.data(), mean0.data(), m20.data(),
+                      cnt0.data(), mean0.data(), m2.data(), cnt.data(), st) == RP_EINVAL);
+  rp_reproject_params rp{};
+  rp.normal_cos = 1.5;
+  CHECK(rph_reproject(&rp, W, H, &cur, &prev, dep.data(), nrm.data(), dep.data(), nrm.data(), mean0.data(), m20.data(),
+                      cnt0.data(), mean.data(), m2.data(), cnt.data(), st) == RP_EINVAL);
+  CHECK(rph_accum_frames_counts(n, 3, 2, fr.data(), 3 * n, cnt.data(), mean.data(), m2.data(), var.data(), -1.0) == RP_EINVAL);
+  std::printf("reproject: a sideways step with sky, empty and long histories, then the per-pixel fold; a camera facing away;\n"
+              "one frame from nothing; in-place, a cosine above 1 and a negative var_one refused\n");
+}
+
 int main(int argc, char** argv) {
   const std::string dir = argc > 1 ? argv[1] : "/tmp";
   check_plan();
   check_unit_walk();
   check_denoise();
   check_tiles();
+  check_reproject();
   MeshScene a = soup(200000, 11);  // >= 2^16 primitives: the parallel build form (rp_bvh.cpp ParallelBuild) runs
   check_tree("soup", a.desc);
   MeshScene b = grid_with_degenerates(40, 3);
