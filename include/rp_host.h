@@ -114,8 +114,9 @@ int rph_plan_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_
 /* Test hook: one round of a draw of the render kernel (raytracing-potato_amd/csrc/rp_draw.h, the same header the
  * kernel's scatter and camera draws use: window addressing with the ring's mirror tail, the stride, the accept rules,
  * "first accepted try wins", the position update).  kind: 1 UnitSphere (Lambert), 2 UnitBall (Metal), 3 the
- * Bernoulli draw's Standard f64 (Dielectric), 4 UnitDisk (camera).  ring_image: a lane's ring exactly as its slab
- * holds it -- 16 * ring_blocks words (ring_blocks 4 or 8; keystream block b in slot b % ring_blocks), then, for
+ * Bernoulli draw's Standard f64 (Dielectric), 4 UnitDisk (camera).  ring_image: a lane's ring laid out as its slab
+ * holds it, in raw keystream words (the hook decodes every u64 to the double the slab keeps, as the kernel does where
+ * it makes a block: rph_draw_values) -- 16 * ring_blocks words (ring_blocks 4 or 8; keystream block b in slot b % ring_blocks), then, for
  * ring_blocks 8, the tail, the first 8 words of slot 0 again (the ring of 4 has none: 64 words are read, wrapping) --
  * which must hold every block the round can consume from the even stream word
  * `pos` on (two tries of 4 words for kinds 1 and 4, of 6 for kind 2; 2 words for kind 3).  On return *accepted tells
@@ -125,6 +126,13 @@ int rph_plan_launch(uint32_t width, uint32_t height, uint32_t spp, uint32_t max_
  * for a bad kind, ring size or odd pos. */
 int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_image, uint32_t pos, double out[3],
                    uint32_t* new_pos, uint32_t* accepted);
+
+/* Test hook: what the kernel's keystream ring holds for a keystream u64 and what a Standard f64 draw makes of it
+ * (rp_draw.h value_store / unit_of, the pair the kernel compiles).  The kernel decodes a block once, where it is made:
+ * with k = u64 >> 11, stored[i] = k 2^-52 - 1 (the rejection samplers' 2 r - 1), and unit[i] = (stored[i] + 1) / 2 =
+ * k 2^-53 (r itself: the jitter, the Bernoulli draw), both exact.  words: n u64 (low word = the first keystream word).
+ * rph_draw_round takes the raw image and decodes it the same way.  RP_EINVAL for a NULL pointer with n > 0. */
+int rph_draw_values(const uint64_t* words, uint64_t n, double* stored, double* unit);
 
 /* Test hook: how a ray enters the conservative f32 box test (raytracing-potato_amd/csrc/rp_ray.h, the same header the
  * kernels' setup_ray32 and trav_step use, except that the reciprocal is a correctly rounded 1 / x here).  rays: n x 8

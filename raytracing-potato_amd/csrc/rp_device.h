@@ -217,7 +217,9 @@ RPK_INLINE void seed_key(uint64_t state, uint32_t key[8]) {
 //
 // Slab layout per lane (uint4 units): [0,2) key words, [2, 2+4*RING) ring (block b in slot b % RING),
 // [2+4*RING, +2) the ring's mirror tail (the first 8 words of slot 0 again, so a draw's window reads straight on past
-// the ring's end: rp_draw.h; the ring of 8 blocks only), then 8 of jitter blocks (block b in slot b & 1).  Per-lane cursors (LDS): end = one
+// the ring's end: rp_draw.h; the ring of 8 blocks only), then 8 of jitter blocks (block b in slot b & 1).  A block is
+// held decoded: each of its 8 u64 as the double 2 r - 1 in the same 8 bytes (ring_values below), in the ring, the tail
+// and the jitter blocks alike.  Per-lane cursors (LDS): end = one
 // past the newest ring block; jtag[2] = block held by each jitter slot.
 static constexpr uint32_t RING = 8;  // slab ring capacity; a kernel keeps RngT::ring <= RING blocks ahead
 static constexpr uint32_t SLAB_KEY = 0, SLAB_RING = 2;  // (the tail and the jitter blocks follow the ring: RngT)
@@ -257,27 +259,32 @@ RPK_INLINE void store_key(Rng& r, const uint32_t k[8]) {
   r.slab[SLAB_KEY] = make_uint4(k[0], k[1], k[2], k[3]);
   r.slab[SLAB_KEY + 1] = make_uint4(k[4], k[5], k[6], k[7]);
 }
-RPK_INLINE void store_block(uint4* dst, const uint32_t w[16]) {
+// A stored block: the slab keeps every keystream u64 decoded (rp_draw.h value_store: the double 2 r - 1), in the u64's
+// 8 bytes.  ring_values is the one place a ChaCha block becomes what the slab holds: every block store below takes its
+// result (a lane's own block and an executor's in rng_refill, a fresh unit's second copy in jitter slot 0, gen_block),
+// so the decode runs once per u64, where the block is made.  The slab stays an array of uint4: a double crosses as its
+// two words (value_bits / bits_value: register names, no instruction).
+RPK_INLINE void ring_values(const uint32_t w[16], double v[8]) {
 #pragma unroll
-  for (int q = 0; q < 4; q++) {
-    dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  }
+  for (int q = 0; q < 8; q++) v[q] = rpd::value_store(w[2 * q], w[2 * q + 1]);
+}
+RPK_INLINE uint4 value_bits(double a, double b) {
+  const uint64_t x = (uint64_t)__double_as_longlong(a), y = (uint64_t)__double_as_longlong(b);
+  return make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32));
+}
+RPK_INLINE double bits_value(uint32_t lo, uint32_t hi) { return __longlong_as_double((long long)((uint64_t)hi << 32 | lo)); }
+RPK_INLINE void store_block(uint4* dst, const double v[8]) {
+#pragma unroll
+  for (int q = 0; q < 4; q++) dst[q] = value_bits(v[2 * q], v[2 * q + 1]);
 }
 // Every store of a ring block goes through here (a lane's own block and an executor's in rng_refill, the in-place
 // fallback gen_block): `tail` is the ring's mirror tail when the block's slot is 0 (ring_tail), else null -- the tail
-// then stays the copy of slot 0's first words that the draw windows rely on.
-RPK_INLINE void store_ring_block(uint4* dst, uint4* tail, const uint32_t w[16]) {
-  store_block(dst, w);
+// then stays the copy of slot 0's first values that the draw windows rely on.
+RPK_INLINE void store_ring_block(uint4* dst, uint4* tail, const double v[8]) {
+  store_block(dst, v);
   if (tail) {
 #pragma unroll
-    for (uint32_t q = 0; q < rpd::TAIL_WORDS / 4; q++) tail[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  }
-}
-RPK_INLINE void load_block(const uint4* src, uint32_t w[16]) {
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const uint4 v = src[q];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    for (uint32_t q = 0; q < rpd::TAIL_WORDS / 4; q++) tail[q] = value_bits(v[2 * q], v[2 * q + 1]);
   }
 }
 template <uint32_t RN>
@@ -357,11 +364,13 @@ RPK_INLINE void rng_refill(RngT<RN>& r, bool alive, bool fresh, uint64_t seed, u
     }
     const uint32_t bb = room ? b : oend + j;
     chacha12(k, bb, w);
+    double v[8];
+    ring_values(w, v);  // decoded here, once, for every site that draws from the block (rp_draw.h value_store)
     // an executor's block goes into its owner's ring (lane slabs are consecutive within the block)
     uint4* oslab = r.slab + ((int)owner - (int)lane) * (int)RngT<RN>::lane_n;  // room: owner == lane
     uint4* dst = room && !main ? jit_slot(r, b) : oslab + SLAB_RING + 4u * (bb & (RN - 1u));
-    store_ring_block(dst, room && !main ? nullptr : ring_tail<RN>(oslab, bb), w);
-    if (fresh) store_block(jit_slot(r, 0), w);  // block 0 is also the jitter block of samples 0-3 (render.rs:74-82)
+    store_ring_block(dst, room && !main ? nullptr : ring_tail<RN>(oslab, bb), v);
+    if (fresh) store_block(jit_slot(r, 0), v);  // block 0 is also the jitter block of samples 0-3 (render.rs:74-82)
   }
   if (room) {
     if (fresh) {
@@ -389,18 +398,23 @@ static __device__ __attribute__((noinline, unused)) void gen_block(const uint4* 
   const uint32_t k[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
   uint32_t w[16];
   chacha12(k, b, w);
-  store_ring_block(dst, tail, w);
+  double v[8];
+  ring_values(w, v);
+  store_ring_block(dst, tail, v);
 }
 
+// The two stored values of sample s's jitter (2 r - 1 each; start_sample takes rpd::unit_of of them) in jv[0], jv[1].
 template <uint32_t RN>
-RPK_INLINE uint4 rng_jitter(RngT<RN>& r, uint32_t s) {
+RPK_INLINE void rng_jitter(RngT<RN>& r, uint32_t s, double jv[2]) {
   const uint32_t b = s >> 2;
   if (r.jtag[(b & 1u) * BLOCK] != b) {
     DREG(DREG_JIT_FALLBACK)
     gen_block(r.slab, b, jit_slot(r, b), nullptr);
     r.jtag[(b & 1u) * BLOCK] = b;
   }
-  return jit_slot(r, b)[s & 3u];
+  const uint4 w = jit_slot(r, b)[s & 3u];
+  jv[0] = bits_value(w.x, w.y);
+  jv[1] = bits_value(w.z, w.w);
 }
 
 // Every draw reads the ring directly: the RN blocks of a lane are one circular run of 16 RN words in its slab
@@ -419,21 +433,21 @@ static_assert((RING & (RING - 1)) == 0, "the ring is indexed as 16 * ring words 
 typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));  // a window starts on an even word
 template <uint32_t STRIDE, uint32_t RN>
 RPK_INLINE void ring_window(const RngT<RN>& r, uint32_t a, rpd::Try& t) {  // stream words a .. a + STRIDE - 1
-  t.w[4] = 0; t.w[5] = 0;
+  t.v[2] = 0.0;
   if constexpr (RngT<RN>::tail_n != 0) {
     const char* p = reinterpret_cast<const char*>(r.slab + SLAB_RING) + 4u * rpd::value_word(a, 0, RN);
     const u32x4_a8 v = *reinterpret_cast<const u32x4_a8*>(p);
-    t.w[0] = v.x; t.w[1] = v.y; t.w[2] = v.z; t.w[3] = v.w;
+    t.v[0] = bits_value(v.x, v.y); t.v[1] = bits_value(v.z, v.w);
     if (STRIDE == 6u) {
       const uint2 z = *reinterpret_cast<const uint2*>(p + 16);
-      t.w[4] = z.x; t.w[5] = z.y;
+      t.v[2] = bits_value(z.x, z.y);
     }
   } else {  // no tail: one wrapped dwordx2 per value
     const uint2* ring = reinterpret_cast<const uint2*>(r.slab + SLAB_RING);
 #pragma unroll
     for (uint32_t k = 0; k < STRIDE / 2u; k++) {
       const uint2 v = ring[rpd::value_word(a, k, RN) >> 1];
-      t.w[2 * k] = v.x; t.w[2 * k + 1] = v.y;
+      t.v[k] = bits_value(v.x, v.y);
     }
   }
 }
@@ -456,13 +470,13 @@ RPK_INLINE bool ring_round(RngT<RN>& r, uint32_t a, rpd::Draw& q) {
   for (uint32_t j = 0; j < TRIES; j++) ring_window<STRIDE>(r, a + STRIDE * j, t[j]);
   return rpd::draw_pick(STRIDE, a, t, q, r.pos);
 }
-// One Standard f64 draw (rand 0.8 gen::<f64>): the u64 at the window address of r.pos
+// One Standard f64 draw (rand 0.8 gen::<f64>): from the stored value at the window address of r.pos
 template <uint32_t RN>
 RPK_INLINE double gen_f64(RngT<RN>& r) {
   ring_ensure(r, r.pos >> 4);
   const uint2 v = reinterpret_cast<const uint2*>(r.slab + SLAB_RING)[rpd::window_word(r.pos, RN) >> 1];
   r.pos += 2;
-  return rpd::words_unit(v.x, v.y);
+  return rpd::unit_of(bits_value(v.x, v.y));
 }
 
 // ------------------------------------------------------------------ math -------------------------
@@ -1580,10 +1594,10 @@ template <class R>
 RPK_INLINE void start_sample(R& rng, uint32_t s, uint32_t pi, uint32_t pj, V3& o, V3& d) {
   DREG(DREG_START_SAMPLE)
   KArgsPtr A = kargs();
-  const uint4 jw = rng_jitter(rng, s);
-  const uint32_t w0 = jw.x, w1 = jw.y, w2 = jw.z, w3 = jw.w;
-  const double ju = ((double)pi + rpd::words_unit(w0, w1)) / (double)A->P.W;
-  const double jv = ((double)pj + rpd::words_unit(w2, w3)) / (double)A->P.H;
+  double jw[2];
+  rng_jitter(rng, s, jw);
+  const double ju = ((double)pi + rpd::unit_of(jw[0])) / (double)A->P.W;
+  const double jv = ((double)pj + rpd::unit_of(jw[1])) / (double)A->P.H;
   // UnitDisk (randomness.rs:21-34): tries of 2 draws, TRIES per round (see ring_round)
   rpd::Draw q;
   for (uint32_t a = rng.pos;; a += 4u * TRIES) {

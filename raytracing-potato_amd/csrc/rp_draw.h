@@ -10,6 +10,8 @@
 // plus a dwordx2 for the third value): the tail lets a window that starts in the ring's last words read straight on.
 // A ring without one (the q8 kernel's 4 blocks) reads each value with its own wrapped address.
 // Bernoulli (Dielectric, randomness.rs:78-82) is one Standard f64, the u64 at ring word a % ring.
+// The ring holds every u64 already decoded, as the double 2 r - 1 (value_store below): a try's values are loaded, not
+// computed, and a draw that wants r takes unit_of of the loaded double.
 //
 // The kernel (rp_device.h scatter_eval, start_sample) and the host test hook (rp_host.h rph_draw_round) both use this
 // header, so the addressing, the accept rules and the position update tested on the CPU are the kernel's.
@@ -64,8 +66,21 @@ RPD_FN double words_sym(uint32_t lo, uint32_t hi) {
   return __builtin_fma((double)hi, 0x1p-31, __builtin_fma((double)(lo >> 11), 0x1p-52, -1.0));
 }
 
+
+// What the ring holds.  The ring, its mirror tail and the jitter blocks keep, for every keystream u64, not the raw
+// words but the double the rejection samplers want, 2 r - 1: the decode (a shift, two conversions, two FMAs) depends on
+// nothing but the u64, so it runs once where the block is made -- in the refill pass, at most of a wave's lanes, for
+// values their lanes will consume -- and not at the draw sites, the kernel's emptiest code, where a wave pays it per
+// round whether nine lanes need it or sixty-four.  The double takes the u64's 8 bytes at its address.
+RPD_FN double value_store(uint32_t lo, uint32_t hi) { return words_sym(lo, hi); }
+// The Standard f64 r from a stored value v, for the draws that want r itself (the jitter, Bernoulli).  Exact:
+// v = k * 2^-52 - 1 with k < 2^53, so v + 1 = k * 2^-52 is representable (k fits the significand) and the sum returns
+// it; halving moves the exponent only (k * 2^-53 is 0 or >= 2^-53, far from subnormal).  So
+// unit_of(value_store(lo, hi)) has the bits of words_unit(lo, hi) (tests/test_draw_values.py).
+RPD_FN double unit_of(double v) { return (v + 1.0) * 0.5; }
+
 struct Try {
-  uint32_t w[WINDOW_WORDS];  // the window's raw words; w[4], w[5] are loaded and read only for stride 6
+  double v[WINDOW_WORDS / 2];  // the window's stored values; v[2] is loaded only for stride 6, 0 otherwise
 };
 struct Draw {
   double x, y, z;  // the accepted try (z = 0 for stride 4)
@@ -78,10 +93,10 @@ RPD_FN bool draw_pick(uint32_t stride, uint32_t a, const Try t[TRIES], Draw& out
   bool done = false;
   RPD_UNROLL
   for (int j = (int)TRIES - 1; j >= 0; j--) {  // descending: the first accepted try wins
-    const double x = words_sym(t[j].w[0], t[j].w[1]), y = words_sym(t[j].w[2], t[j].w[3]);
+    const double x = t[j].v[0], y = t[j].v[1];
     double z = 0.0, s = x * x + y * y;
     if (stride == 6u) {
-      z = words_sym(t[j].w[4], t[j].w[5]);
+      z = t[j].v[2];
       s = s + z * z;
     }
     if (s < 1.0) {

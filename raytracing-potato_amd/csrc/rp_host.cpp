@@ -883,9 +883,12 @@ int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_ima
       !ring_image || !out || !new_pos || !accepted)
     return fail("rph_draw_round: kind 1-4, ring_blocks 4 or 8, even pos, non-NULL pointers");
   out[0] = out[1] = out[2] = 0.0;
-  if (kind == rpd::DRAW_UNIFORM) {  // the kernel's gen_f64: the u64 at the window address
-    const uint32_t* p = ring_image + rpd::window_word(pos, ring_blocks);
-    out[0] = rpd::words_unit(p[0], p[1]);
+  // the raw image as the kernel's slab holds it: every u64 decoded where its block is made (rp_device.h ring_values)
+  double held[(16u * 8u + rpd::TAIL_WORDS) / 2u];
+  for (uint32_t i = 0; i < rpd::ring_image_words(ring_blocks) / 2u; i++)
+    held[i] = rpd::value_store(ring_image[2 * i], ring_image[2 * i + 1]);
+  if (kind == rpd::DRAW_UNIFORM) {  // the kernel's gen_f64: from the stored value at the window address
+    out[0] = rpd::unit_of(held[rpd::window_word(pos, ring_blocks) >> 1]);
     *new_pos = pos + 2u;
     *accepted = 1u;
     return RP_OK;
@@ -893,12 +896,8 @@ int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_ima
   const uint32_t stride = rpd::draw_stride(kind);
   rpd::Try t[rpd::TRIES];
   for (uint32_t j = 0; j < rpd::TRIES; j++) {  // the kernel's ring_window
-    for (uint32_t q = 0; q < rpd::WINDOW_WORDS; q++) t[j].w[q] = 0u;
-    for (uint32_t k = 0; k < stride / 2u; k++) {
-      const uint32_t* p = ring_image + rpd::value_word(pos + stride * j, k, ring_blocks);
-      t[j].w[2 * k] = p[0];
-      t[j].w[2 * k + 1] = p[1];
-    }
+    for (uint32_t k = 0; k < rpd::WINDOW_WORDS / 2u; k++) t[j].v[k] = 0.0;
+    for (uint32_t k = 0; k < stride / 2u; k++) t[j].v[k] = held[rpd::value_word(pos + stride * j, k, ring_blocks) >> 1];
   }
   rpd::Draw d{0.0, 0.0, 0.0, 0.0};
   uint32_t np = pos + stride * rpd::TRIES;
@@ -911,6 +910,15 @@ int rph_draw_round(uint32_t kind, uint32_t ring_blocks, const uint32_t* ring_ima
     } else {
       out[0] = d.x; out[1] = d.y; out[2] = d.z;
     }
+  }
+  return RP_OK;
+}
+
+int rph_draw_values(const uint64_t* words, uint64_t n, double* stored, double* unit) {
+  if (n && (!words || !stored || !unit)) return fail("rph_draw_values: non-NULL pointers");
+  for (uint64_t i = 0; i < n; i++) {
+    stored[i] = rpd::value_store((uint32_t)words[i], (uint32_t)(words[i] >> 32));
+    unit[i] = rpd::unit_of(stored[i]);
   }
   return RP_OK;
 }

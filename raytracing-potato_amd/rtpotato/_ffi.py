@@ -216,7 +216,7 @@ HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
                 "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
                 "rph_tiles_unit_walk", "rph_material_head", "rph_scene_materials", "rph_reproject",
-                "rph_accum_frames_counts"]
+                "rph_accum_frames_counts", "rph_draw_values"]
 
 
 def rp_lib_path() -> str:
@@ -380,6 +380,7 @@ def host() -> ctypes.CDLL:
     lib.rph_make_div32.argtypes = [c_uint32, POINTER(c_uint32), POINTER(c_uint32)]
     lib.rph_draw_round.argtypes = [c_uint32, c_uint32, c_void_p, c_uint32, c_void_p, POINTER(c_uint32),
                                    POINTER(c_uint32)]
+    lib.rph_draw_values.argtypes = [c_void_p, c_uint64, c_void_p, c_void_p]
     lib.rph_ray_setup.argtypes = [c_uint32, c_double, c_void_p, c_uint64, c_void_p]
     lib.rph_prim_test.argtypes = [c_uint32, c_void_p, c_void_p, c_uint64, c_void_p]
     lib.rph_plan_launch.argtypes = [c_uint32] * 14 + [c_uint64, POINTER(rph_launch_plan)]
