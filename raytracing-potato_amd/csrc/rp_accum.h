@@ -4,10 +4,18 @@
 //
 // Every value is IEEE binary64, every expression is written in the operation order include/rp.h gives and compiled
 // without contraction (-ffp-contract=off), only + - * / and comparisons, so the kernels (rp_accum.hip), the CPU loops
-// behind rph_accum_frames and rph_accum_error (rp_host.cpp) and the numpy model of the tests (tests/accum_ref.py, written
-// from the definition and not from this file) agree to the last bit.
+// behind rph_accum_frames and rph_accum_error (rp_host_passes.cpp) and the numpy model of the tests (tests/accum_ref.py,
+// written from the definition and not from this file) agree to the last bit.
+//
+// Below the arithmetic: what the folds and the tile selection refuse about their arguments, for both libraries -- plain
+// host functions that return the reason (NULL: fine), which the device entry points hand to fail() and the host ones
+// prefix with their name.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/rp.h"
+#include "rp_kernel.h"
+#include "rp_overlap.h"
 
 #if defined(__HIPCC__)
 #define RPA_FN __host__ __device__ __forceinline__
@@ -69,5 +77,87 @@ RPA_FN bool tile_active(uint32_t over, uint32_t px, double tile_share) {
 // The four statistics of an error pass (RP_ERROR_STATS_LEN): all order-free -- integer sums and an integer maximum of
 // the bit patterns of positive doubles, which order as the doubles do.
 enum { STAT_PIXELS = 0, STAT_OVER = 1, STAT_MAX_BITS = 2, STAT_NONFINITE = 3, STATS_LEN = 4 };
+
+// ---- the entry points' refusals (host side of both libraries)
+
+constexpr uint64_t MAX_WORDS = (1ull << 40) - 512;  // of a fold's state: its lanes fit 2^31 - 1 blocks of 256
+
+// frames, then mean, m2 and var (NULL: not wanted) of state_bytes each: no output aliases the frames, nor another.
+inline const char* check_state_alias(const double* frames, uint64_t in_bytes, const double* mean, const double* m2,
+                                     const double* var, uint64_t state_bytes) {
+  using rpo::overlaps;
+  if (overlaps(mean, state_bytes, frames, in_bytes) || overlaps(m2, state_bytes, frames, in_bytes) ||
+      overlaps(var, state_bytes, frames, in_bytes))
+    return "mean, m2 and var must not alias the frames";
+  if (overlaps(mean, state_bytes, m2, state_bytes) || overlaps(var, state_bytes, mean, state_bytes) ||
+      overlaps(var, state_bytes, m2, state_bytes))
+    return "mean, m2 and var must not alias one another";
+  return nullptr;
+}
+
+// The plain and the tile fold.  A frame of the call holds n_in blocks of block_words words and the state (mean, m2, var)
+// n_state such blocks.  The plain fold (listed = false) is one block of n_words in both, without a list; the tile fold
+// n_listed and n_state_tiles blocks of tile_words, tiles naming the state block of each listed one.  n_in = 0 (an empty
+// list) is fine: nothing is read, so nothing can alias.
+inline const char* check_fold(bool listed, uint64_t block_words, uint32_t n_in, uint32_t n_state, const uint32_t* tiles,
+                              uint32_t n_prior, uint32_t n_frames, const double* frames, uint64_t frame_stride,
+                              const double* mean, const double* m2, const double* var) {
+  if (!frames || !mean || !m2) return "frames, mean and m2 must be non-NULL";
+  if (block_words == 0) return listed ? "tile_words is zero" : "n_words is zero";
+  if (n_in > n_state) return "n_listed is above n_state_tiles";
+  if (listed && n_in && !tiles) return "tiles must be non-NULL";
+  if (block_words > MAX_WORDS / (n_state ? n_state : 1u))
+    return "the state is above 2^40 - 512 words (n_words, or n_state_tiles * tile_words)";
+  if (n_frames == 0) return "n_frames is zero: nothing to fold in";
+  const uint64_t in_words = n_in * block_words;
+  if (frame_stride < in_words)
+    return "frame_stride is below a frame's words (n_words, or n_listed * tile_words): the frames would overlap";
+  const uint64_t n = (uint64_t)n_prior + n_frames;
+  if (n > 0x7fffffffu) return "more than 2^31 - 1 frames (n_prior + n_frames)";
+  if (var && n < 2) return "the variance needs at least two frames (n_prior + n_frames >= 2)";
+  if (n_in == 0) return nullptr;
+  // byte counts: the words are below 2^40 here; a stride that wraps 64 bits is the caller's address space running out
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + in_words);
+  const uint64_t state_bytes = 8 * ((uint64_t)n_state * block_words), list_bytes = 4ull * n_in;
+  if (rpo::overlaps(mean, state_bytes, tiles, list_bytes) || rpo::overlaps(m2, state_bytes, tiles, list_bytes) ||
+      rpo::overlaps(var, state_bytes, tiles, list_bytes))
+    return "mean, m2 and var must not alias the list";
+  return check_state_alias(frames, in_bytes, mean, m2, var, state_bytes);
+}
+
+// The fold with the frame number taken per pixel.
+inline const char* check_fold_counts(uint64_t n_pixels, uint32_t words_per_pixel, uint32_t n_frames, const double* frames,
+                                     uint64_t frame_stride, const uint32_t* count, const double* mean, const double* m2,
+                                     const double* var, double var_one) {
+  using rpo::overlaps;
+  if (!frames || !mean || !m2 || !count) return "frames, count, mean and m2 must be non-NULL";
+  if (n_pixels == 0 || words_per_pixel == 0) return "n_pixels or words_per_pixel is zero";
+  if (n_frames == 0) return "n_frames is zero: nothing to fold in";
+  if (n_frames > 0x7fffffffu) return "more than 2^31 - 1 frames";
+  if (n_pixels > MAX_WORDS / words_per_pixel) return "n_pixels * words_per_pixel is above 2^40 - 512";
+  const uint64_t n_words = n_pixels * words_per_pixel;
+  if (frame_stride < n_words) return "frame_stride is below n_pixels * words_per_pixel: the frames would overlap";
+  if (!(var_one >= 0.0 && finite(var_one))) return "var_one must be finite and >= 0";
+  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), state_bytes = 8 * n_words;
+  const uint64_t count_bytes = 4 * n_pixels;
+  if (const char* why = check_state_alias(frames, in_bytes, mean, m2, var, state_bytes)) return why;
+  if (overlaps(count, count_bytes, frames, in_bytes) || overlaps(count, count_bytes, mean, state_bytes) ||
+      overlaps(count, count_bytes, m2, state_bytes) || overlaps(count, count_bytes, var, state_bytes))
+    return "count must not alias the frames or the state";
+  return nullptr;
+}
+
+// Tile selection, after the frame's tiling is made: the state is a whole frame's (shards, shard_map: the tiling's and
+// the params'), the error params resolve into tol and eps, tile_share is in [0, 1) and the list fits the compaction.
+template <class P>
+inline const char* check_select(uint32_t shards, uint32_t shard_map, const P* error, double tile_share, uint32_t n_in,
+                                double& tol, double& eps) {
+  if (shards != 1 || shard_map != RP_SHARD_INTERLEAVE)
+    return "the state is a whole frame's: num_shards 0 or 1, shard 0, interleave";
+  if (!resolve(error, tol, eps)) return "error params out of range (tol > 0; eps > 0 and finite)";
+  if (!(tile_share >= 0.0 && tile_share < 1.0)) return "tile_share must be in [0, 1)";
+  if (n_in > (uint32_t)rpk::TILE_SORT_MAX) return "n_in is above 16384 (rpk::TILE_SORT_MAX)";
+  return nullptr;
+}
 
 }  // namespace rpa

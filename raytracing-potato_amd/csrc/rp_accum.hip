@@ -261,42 +261,17 @@ __global__ void __launch_bounds__(ERR_BLOCK) error_kernel(const ErrArgs A) {
   }
 }
 
-// What both folds refuse about their frame counts and their buffers, and the kernel's arguments.  A frame of the call
-// holds n_in blocks of block_words words and the state (d_mean, d_m2, d_var) n_state such blocks: the plain fold is one
-// block of n_words in both, without a list; the tile fold n_listed and n_state_tiles blocks of tile_words, with d_tiles
-// naming the state block of each listed one.  n_in = 0 (an empty list): nothing is read or launched, so nothing can
-// alias.
-static int fold_args(uint64_t block_words, uint32_t n_in, uint32_t n_state, const uint32_t* d_tiles, uint32_t n_prior,
-                     uint32_t n_frames, const double* d_frames, uint64_t frame_stride, double* d_mean, double* d_m2,
-                     double* d_var, AccArgs& a) {
-  using rpp::overlaps;
-  const uint64_t in_words = n_in * block_words, state_words = n_state * block_words;
-  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
-  if (frame_stride < in_words)
-    return fail(RP_EINVAL, d_tiles ? "frame_stride is below n_listed * tile_words: the frames would overlap"
-                                   : "frame_stride is below n_words: the frames would overlap");
-  const uint64_t n = (uint64_t)n_prior + n_frames;
-  if (n > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames (n_prior + n_frames)");
-  if (d_var && n < 2) return fail(RP_EINVAL, "the variance needs at least two frames (n_prior + n_frames >= 2)");
-  if (n_in == 0) return RP_OK;
-  // byte counts: the words are below 2^40 here; a stride that wraps 64 bits is the caller's address space running out
-  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + in_words), out_bytes = 8 * state_words;
-  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
-    if (overlaps(o, out_bytes, d_frames, in_bytes) || overlaps(o, out_bytes, d_tiles, 4ull * n_in))
-      return fail(RP_EINVAL, d_tiles ? "d_mean, d_m2 and d_var must not alias the frames or the list"
-                                     : "d_mean, d_m2 and d_var must not alias the frames");
-  if (overlaps(d_mean, out_bytes, d_m2, out_bytes) || overlaps(d_var, out_bytes, d_mean, out_bytes) ||
-      overlaps(d_var, out_bytes, d_m2, out_bytes))
-    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
+// The kernel's arguments of both folds, once rp_accum.h's check_fold has admitted the call; listed: the tile fold.
+static void fold_args(bool listed, uint64_t block_words, uint32_t n_prior, uint32_t n_frames, const double* d_frames,
+                      uint64_t frame_stride, double* d_mean, double* d_m2, double* d_var, AccArgs& a) {
   a.n_words = block_words, a.stride = frame_stride;
   a.n_prior = n_prior, a.n_frames = n_frames;
   const uintptr_t bits = reinterpret_cast<uintptr_t>(d_frames) | reinterpret_cast<uintptr_t>(d_mean) |
                          reinterpret_cast<uintptr_t>(d_m2) | reinterpret_cast<uintptr_t>(d_var);
   // the wide path: every block starts on an even word of 16-byte aligned buffers, in the frames and in the state (the
   // plain fold's one block starts each frame: an even stride is enough)
-  a.vec = bits % 16 == 0 && frame_stride % 2 == 0 && (d_tiles == nullptr || block_words % 2 == 0);
+  a.vec = bits % 16 == 0 && frame_stride % 2 == 0 && (!listed || block_words % 2 == 0);
   a.frames = d_frames, a.mean = d_mean, a.m2 = d_m2, a.var = d_var;
-  return RP_OK;
 }
 
 }  // namespace rpa
@@ -305,13 +280,13 @@ extern "C" {
 
 int rp_accum_frames_device(uint64_t n_words, uint32_t n_prior, uint32_t n_frames, const double* d_frames,
                            uint64_t frame_stride, double* d_mean, double* d_m2, double* d_var, void* stream) {
-  if (!d_frames || !d_mean || !d_m2) return fail(RP_EINVAL, "d_frames, d_mean and d_m2 must be non-NULL");
-  if (n_words == 0) return fail(RP_EINVAL, "n_words is zero");
+  if (const char* why = rpa::check_fold(false, n_words, 1, 1, nullptr, n_prior, n_frames, d_frames, frame_stride, d_mean,
+                                        d_m2, d_var))
+    return fail(RP_EINVAL, why);
   const uint64_t lanes = (n_words + 1) / 2, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
-  if (grid > 0x7fffffffu) return fail(RP_EINVAL, "n_words is above 2^40 - 512: more than 2^31 - 1 blocks");
+  if (grid > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 blocks");
   rpa::AccArgs a;
-  const int rc = rpa::fold_args(n_words, 1, 1, nullptr, n_prior, n_frames, d_frames, frame_stride, d_mean, d_m2, d_var, a);
-  if (rc) return rc;
+  rpa::fold_args(false, n_words, n_prior, n_frames, d_frames, frame_stride, d_mean, d_m2, d_var, a);
   hipLaunchKernelGGL(rpa::accum_kernel, dim3((unsigned)grid), dim3(rpa::ACC_BLOCK), 0, (hipStream_t)stream, a);
   RP_HIP(hipGetLastError());
   return RP_OK;
@@ -320,17 +295,12 @@ int rp_accum_frames_device(uint64_t n_words, uint32_t n_prior, uint32_t n_frames
 int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, const uint32_t* d_tiles, uint32_t n_listed,
                                  uint32_t n_prior, uint32_t n_frames, const double* d_frames, uint64_t frame_stride,
                                  double* d_mean, double* d_m2, double* d_var, void* stream) {
-  if (!d_frames || !d_mean || !d_m2) return fail(RP_EINVAL, "d_frames, d_mean and d_m2 must be non-NULL");
-  if (tile_words == 0) return fail(RP_EINVAL, "tile_words is zero");
-  if (n_listed > n_state_tiles) return fail(RP_EINVAL, "n_listed is above n_state_tiles");
-  if (n_listed && !d_tiles) return fail(RP_EINVAL, "d_tiles must be non-NULL");
-  if (tile_words > (1ull << 40) - 512 || (uint64_t)n_state_tiles * tile_words > (1ull << 40) - 512)
-    return fail(RP_EINVAL, "the state is above 2^40 - 512 words (n_state_tiles * tile_words)");
-  rpa::TileArgs t;
-  const int rc = rpa::fold_args(tile_words, n_listed, n_state_tiles, d_tiles, n_prior, n_frames, d_frames, frame_stride,
-                                d_mean, d_m2, d_var, t.A);
-  if (rc) return rc;
+  if (const char* why = rpa::check_fold(true, tile_words, n_listed, n_state_tiles, d_tiles, n_prior, n_frames, d_frames,
+                                        frame_stride, d_mean, d_m2, d_var))
+    return fail(RP_EINVAL, why);
   if (n_listed == 0) return RP_OK;  // nothing listed: nothing folded, nothing launched
+  rpa::TileArgs t;
+  rpa::fold_args(true, tile_words, n_prior, n_frames, d_frames, frame_stride, d_mean, d_m2, d_var, t.A);
   t.tiles = d_tiles, t.n_listed = n_listed, t.n_state = n_state_tiles;
   t.lanes_per_tile = (tile_words + 1) / 2;
   const uint64_t lanes = t.lanes_per_tile * n_listed, grid = (lanes + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;
@@ -343,28 +313,9 @@ int rp_accum_frames_tiles_device(uint64_t tile_words, uint32_t n_state_tiles, co
 int rp_accum_frames_counts_device(uint64_t n_pixels, uint32_t words_per_pixel, uint32_t n_frames, const double* d_frames,
                                   uint64_t frame_stride, uint32_t* d_count, double* d_mean, double* d_m2, double* d_var,
                                   double var_one, void* stream) {
-  using rpp::overlaps;
-  if (!d_frames || !d_mean || !d_m2 || !d_count)
-    return fail(RP_EINVAL, "d_frames, d_count, d_mean and d_m2 must be non-NULL");
-  if (n_pixels == 0 || words_per_pixel == 0) return fail(RP_EINVAL, "n_pixels or words_per_pixel is zero");
-  if (n_frames == 0) return fail(RP_EINVAL, "n_frames is zero: nothing to fold in");
-  if (n_frames > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 frames");
-  if (n_pixels > ((1ull << 40) - 512) / words_per_pixel)
-    return fail(RP_EINVAL, "n_pixels * words_per_pixel is above 2^40 - 512");
-  const uint64_t n_words = n_pixels * words_per_pixel;
-  if (frame_stride < n_words) return fail(RP_EINVAL, "frame_stride is below n_pixels * words_per_pixel: the frames would overlap");
-  if (!(var_one >= 0.0 && rpa::finite(var_one))) return fail(RP_EINVAL, "var_one must be finite and >= 0");
-  const uint64_t in_bytes = 8 * ((uint64_t)(n_frames - 1) * frame_stride + n_words), out_bytes = 8 * n_words;
-  const uint64_t count_bytes = 4 * n_pixels;
-  for (const double* o : {(const double*)d_mean, (const double*)d_m2, (const double*)d_var})
-    if (overlaps(o, out_bytes, d_frames, in_bytes))
-      return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias the frames");
-  if (overlaps(d_mean, out_bytes, d_m2, out_bytes) || overlaps(d_var, out_bytes, d_mean, out_bytes) ||
-      overlaps(d_var, out_bytes, d_m2, out_bytes))
-    return fail(RP_EINVAL, "d_mean, d_m2 and d_var must not alias one another");
-  if (overlaps(d_count, count_bytes, d_frames, in_bytes) || overlaps(d_count, count_bytes, d_mean, out_bytes) ||
-      overlaps(d_count, count_bytes, d_m2, out_bytes) || overlaps(d_count, count_bytes, d_var, out_bytes))
-    return fail(RP_EINVAL, "d_count must not alias the frames or the state");
+  if (const char* why = rpa::check_fold_counts(n_pixels, words_per_pixel, n_frames, d_frames, frame_stride, d_count, d_mean,
+                                               d_m2, d_var, var_one))
+    return fail(RP_EINVAL, why);
   const uint64_t grid = (n_pixels + rpa::ACC_BLOCK - 1) / rpa::ACC_BLOCK;  // < 2^32: n_pixels is below 2^40
   if (grid > 0x7fffffffu) return fail(RP_EINVAL, "more than 2^31 - 1 blocks");
   rpa::CountArgs a;

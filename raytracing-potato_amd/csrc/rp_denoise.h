@@ -4,7 +4,7 @@
 //
 // Every value is IEEE binary64 and every expression uses + - * /, comparisons and max(|a|, |b|) only, written in the
 // operation order include/rp.h gives and compiled without contraction (-ffp-contract=off), so the kernel
-// (rp_denoise.hip), the CPU loop behind rph_denoise (rp_host.cpp) and the numpy model of the tests
+// (rp_denoise.hip), the CPU loop behind rph_denoise (rp_host_passes.cpp) and the numpy model of the tests
 // (tests/denoise_ref.py, written from the definition and not from this file) agree to the last bit.
 //
 // A caller hands level_step the pixel's own record and a `tap(dx, dy, q)` that fills q with the record of the pixel at
@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/rp.h"
+#include "rp_overlap.h"
 
 #if defined(__HIPCC__)
 #define RPDN_FN __host__ __device__ __forceinline__
@@ -79,6 +80,24 @@ inline bool resolve(const rp_denoise_var_params* in, rp_denoise_var_params& p) {
   for (double x : pos)
     if (!(x > 0.0) || x - x != 0.0) return false;
   return true;
+}
+
+// ---- what every entry point refuses about its frames, device and host; NULL = fine
+inline const char* check_size(uint32_t width, uint32_t height) {
+  if (width == 0 || height == 0 || width > 65535 || height > 65535) return "width and height must be 1..65535";
+  return nullptr;
+}
+// var NULL: the guided denoiser (the variance-guided one refuses a NULL var itself).
+inline const char* check_frames(uint32_t width, uint32_t height, const double* rgb, const double* var, const double* normal,
+                                const double* albedo, const double* depth, const double* out) {
+  if (const char* why = check_size(width, height)) return why;
+  if (!rgb || !out) return "rgb and out must be non-NULL";
+  const uint64_t b1 = 8 * (uint64_t)width * height, b3 = 3 * b1;
+  using rpo::overlaps;
+  if (overlaps(out, b3, rgb, b3) || overlaps(out, b3, normal, b3) || overlaps(out, b3, albedo, b3) ||
+      overlaps(out, b3, depth, b1) || overlaps(out, b3, var, b3))
+    return "out must not alias an input";
+  return nullptr;
 }
 
 // ---- one level's constants (made on the host for both sides)

@@ -125,27 +125,17 @@ __global__ void __launch_bounds__(DN_BLOCK) denoise_level(const DnArgs A) {
 
 namespace {
 
-constexpr uint32_t DIM_MAX = 65535;  // a frame's width and height, as the renders' (rp_schedule.h make_tiling)
-
 using rpp::overlaps;
 
 // Doubles of scratch per pixel: two colour buffers (3 each) and, with the variance, two variance buffers (1 each).
 constexpr uint64_t scratch_doubles(bool var) { return var ? 2 * (3 + 1) : 2 * 3; }
 
-int check_frame(uint32_t width, uint32_t height) {
-  if (width == 0 || height == 0) return fail(RP_EINVAL, "width and height must be >= 1");
-  if (width > DIM_MAX || height > DIM_MAX) return fail(RP_EINVAL, "width and height must be <= 65535");
-  return RP_OK;
-}
-
-// What rp_denoise_device and rp_denoise_var_device refuse about their buffers (d_var NULL: the former).
-int check_buffers(uint32_t width, uint32_t height, const double* d_rgb, const double* d_var, const double* d_normal,
+// The device's own refusals, after rp_denoise.h's check_frames: the scratch of rp_denoise_device and
+// rp_denoise_var_device (d_var NULL: the former).
+int check_scratch(uint32_t width, uint32_t height, const double* d_rgb, const double* d_var, const double* d_normal,
                   const double* d_albedo, const double* d_depth, const double* d_out, const void* d_scratch) {
   const uint64_t n = (uint64_t)width * height, b3 = 3 * n * sizeof(double), b1 = n * sizeof(double);
   const uint64_t scratch_bytes = scratch_doubles(d_var != nullptr) * b1;
-  if (overlaps(d_out, b3, d_rgb, b3) || overlaps(d_out, b3, d_normal, b3) || overlaps(d_out, b3, d_albedo, b3) ||
-      overlaps(d_out, b3, d_depth, b1) || overlaps(d_out, b3, d_var, b3))
-    return fail(RP_EINVAL, "out must not alias an input");
   if (overlaps(d_scratch, scratch_bytes, d_out, b3) || overlaps(d_scratch, scratch_bytes, d_rgb, b3) ||
       overlaps(d_scratch, scratch_bytes, d_normal, b3) || overlaps(d_scratch, scratch_bytes, d_albedo, b3) ||
       overlaps(d_scratch, scratch_bytes, d_depth, b1) || overlaps(d_scratch, scratch_bytes, d_var, b3))
@@ -193,10 +183,8 @@ int launch_levels(const Params& P, uint32_t iterations, uint32_t width, uint32_t
 template <class Enqueue>
 int denoise_sync(int device, uint32_t width, uint32_t height, const double* rgb, const double* var, const double* normal,
                  const double* albedo, const double* depth, double* out, double* seconds, Enqueue enqueue) {
+  if (const char* why = rpdn::check_frames(width, height, rgb, var, normal, albedo, depth, out)) return fail(RP_EINVAL, why);
   const uint64_t n = (uint64_t)width * height;
-  if (overlaps(out, 24 * n, rgb, 24 * n) || overlaps(out, 24 * n, normal, 24 * n) || overlaps(out, 24 * n, albedo, 24 * n) ||
-      overlaps(out, 24 * n, depth, 8 * n) || overlaps(out, 24 * n, var, 24 * n))
-    return fail(RP_EINVAL, "out must not alias an input");
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RP_ENODEV, "no HIP device");
   if (device < 0 || device >= count) return fail(RP_EINVAL, "device out of range");
@@ -235,8 +223,7 @@ int rp_denoise_params_init(rp_denoise_params* p) {
 }
 
 int rp_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
-  int rc = check_frame(width, height);
-  if (rc) return rc;
+  if (const char* why = rpdn::check_size(width, height)) return fail(RP_EINVAL, why);
   if (!bytes) return fail(RP_EINVAL, "bytes is NULL");
   *bytes = scratch_doubles(false) * sizeof(double) * width * height;
   return RP_OK;
@@ -245,23 +232,20 @@ int rp_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
 int rp_denoise_device(const rp_denoise_params* params, uint32_t width, uint32_t height, const double* d_rgb,
                       const double* d_normal, const double* d_albedo, const double* d_depth, double* d_out,
                       void* d_scratch, void* stream) {
-  int rc = check_frame(width, height);
-  if (rc) return rc;
-  if (!d_rgb || !d_out || !d_scratch) return fail(RP_EINVAL, "rgb, out and scratch must be non-NULL");
+  if (const char* why = rpdn::check_frames(width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out))
+    return fail(RP_EINVAL, why);
+  if (!d_scratch) return fail(RP_EINVAL, "scratch must be non-NULL");
   rp_denoise_params P;
   if (!rpdn::resolve(params, P))
     return fail(RP_EINVAL, "denoise params out of range: iterations 1..8, normal_power 1..8, sigma_depth, sigma_albedo "
                            "and albedo_eps > 0 and finite, sigma_color finite (negative disables)");
-  if ((rc = check_buffers(width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out, d_scratch))) return rc;
+  if (const int rc = check_scratch(width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out, d_scratch)) return rc;
   return launch_levels<false>(P, P.iterations, width, height, d_rgb, nullptr, d_normal, d_albedo, d_depth, d_out,
                               d_scratch, stream);
 }
 
 int rp_denoise(const rp_denoise_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
                const double* normal, const double* albedo, const double* depth, double* out, double* seconds) {
-  int rc = check_frame(width, height);
-  if (rc) return rc;
-  if (!rgb || !out) return fail(RP_EINVAL, "rgb and out must be non-NULL");
   rp_denoise_params P;
   if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, "denoise params out of range");
   return denoise_sync(device, width, height, rgb, nullptr, normal, albedo, depth, out, seconds,
@@ -278,8 +262,7 @@ int rp_denoise_var_params_init(rp_denoise_var_params* p) {
 }
 
 int rp_denoise_var_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes) {
-  int rc = check_frame(width, height);
-  if (rc) return rc;
+  if (const char* why = rpdn::check_size(width, height)) return fail(RP_EINVAL, why);
   if (!bytes) return fail(RP_EINVAL, "bytes is NULL");
   *bytes = scratch_doubles(true) * sizeof(double) * width * height;
   return RP_OK;
@@ -288,12 +271,12 @@ int rp_denoise_var_scratch_bytes(uint32_t width, uint32_t height, uint64_t* byte
 int rp_denoise_var_device(const rp_denoise_var_params* params, uint32_t width, uint32_t height, const double* d_rgb,
                           const double* d_var, const double* d_normal, const double* d_albedo, const double* d_depth,
                           double* d_out, void* d_scratch, void* stream) {
-  int rc = check_frame(width, height);
-  if (rc) return rc;
-  if (!d_rgb || !d_var || !d_out || !d_scratch) return fail(RP_EINVAL, "rgb, var, out and scratch must be non-NULL");
+  if (const char* why = rpdn::check_frames(width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out))
+    return fail(RP_EINVAL, why);
+  if (!d_var || !d_scratch) return fail(RP_EINVAL, "var and scratch must be non-NULL");
   rp_denoise_var_params P;
   if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, VAR_RANGE);
-  if ((rc = check_buffers(width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch))) return rc;
+  if (const int rc = check_scratch(width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out, d_scratch)) return rc;
   return launch_levels<true>(P, P.base.iterations, width, height, d_rgb, d_var, d_normal, d_albedo, d_depth, d_out,
                              d_scratch, stream);
 }
@@ -301,9 +284,7 @@ int rp_denoise_var_device(const rp_denoise_var_params* params, uint32_t width, u
 int rp_denoise_var(const rp_denoise_var_params* params, int device, uint32_t width, uint32_t height, const double* rgb,
                    const double* var, const double* normal, const double* albedo, const double* depth, double* out,
                    double* seconds) {
-  int rc = check_frame(width, height);
-  if (rc) return rc;
-  if (!rgb || !var || !out) return fail(RP_EINVAL, "rgb, var and out must be non-NULL");
+  if (!var) return fail(RP_EINVAL, "var must be non-NULL");
   rp_denoise_var_params P;
   if (!rpdn::resolve(params, P)) return fail(RP_EINVAL, VAR_RANGE);
   return denoise_sync(device, width, height, rgb, var, normal, albedo, depth, out, seconds,

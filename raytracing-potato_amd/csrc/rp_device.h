@@ -1560,7 +1560,7 @@ RPK_INLINE KArgsPtr kargs() {
   return p;
 }
 
-// What rp_units.h's unit fetch needs from the place it runs in, on the GPU (the host library has its own, rp_host.cpp).
+// What rp_units.h's unit fetch needs from the place it runs in, on the GPU (the host library has its own, rp_host_sched.cpp).
 // All forced inline, so the fetch reaches the optimizer as the text it was when it stood here.
 struct DevEnv {
   static RPK_INLINE KArgsPtr args() { return kargs(); }

@@ -42,7 +42,7 @@
 // are clamped to |inv| <= 2^64 (axis-parallel rays) and frames to |o|, 255 s <= 2^56 (rp_layout.h
 // COORD_MAX), so every A, B and t^ is finite; an A that underflows errs by < 2^-118, inside the 2^-100 term.
 //
-// The kernel (rp_device.h prim_test, trav_step, trav_step_w8), the CPU model of the traversal (rp_host.cpp
+// The kernel (rp_device.h prim_test, trav_step, trav_step_w8), the CPU model of the traversal (rp_host_tree.cpp
 // rph_bvh_traversal_stats) and the host test hook (rp_host.h rph_prim_test) all use this header.  The device evaluates
 // plane_t and the pass test two children at a time (v_pk_fma_f32: the same fused operation per element) and takes the
 // near and far planes by the slope's sign where the host takes min and max of both (the same pair of values: t^ is

@@ -7,18 +7,14 @@
 #include <cmath>
 #include <cstring>
 
+#include "rp_overlap.h"
 #include "rp_state.h"
 
 #pragma GCC visibility push(hidden)
 
 namespace rpp {
 
-// Byte ranges [a, a + na) and [b, b + nb) share a byte (a NULL pointer is no range).
-inline bool overlaps(const void* a, uint64_t na, const void* b, uint64_t nb) {
-  if (!a || !b) return false;
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
+using rpo::overlaps;  // (rp_overlap.h: the host library's checks use the same one)
 
 // The fields rpk::slot_pixel (rp_units.h) reads to decode a shard slot, under KParams' names, and the slot count: what
 // a kernel with one lane per shard slot takes beside its own arguments.

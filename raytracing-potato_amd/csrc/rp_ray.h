@@ -33,7 +33,7 @@
 // a negative (or NaN) best, for which no hit can be accepted at all, has its sign bit set, so the clamp returns
 // +inf -- conservative (boxes are then culled by their slabs alone).  Three instructions.
 //
-// The kernel (rp_device.h setup_ray32, trav_step), the CPU model of the traversal (rp_host.cpp
+// The kernel (rp_device.h setup_ray32, trav_step), the CPU model of the traversal (rp_host_tree.cpp
 // rph_bvh_traversal_stats) and the host test hook (rp_host.h rph_ray_setup) all use this header, and rp_isect.h for
 // what follows it -- the slab test's frame terms, plane t^ and pass test, and the exact primitive tests -- so the
 // arithmetic tested on the CPU is the kernel's -- except the reciprocal: the device's v_rcp_f32 (<= 1 ulp) against the

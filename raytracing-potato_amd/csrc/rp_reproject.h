@@ -5,11 +5,13 @@
 // Every value is IEEE binary64, every expression is written in the operation order include/rp.h gives and compiled
 // without contraction (-ffp-contract=off), only + - * /, comparisons, floor and sqrt (correctly rounded on both sides,
 // as rp_isect.h's sphere test relies on), so the kernel (rp_reproject.hip), the CPU loop behind rph_reproject
-// (rp_host.cpp) and the numpy model of the tests (tests/reproject_ref.py, written from the definition and not from this
+// (rp_host_passes.cpp) and the numpy model of the tests (tests/reproject_ref.py, written from the definition and not from this
 // file) agree to the last bit.  The two tangents per camera are taken on the host (make_camera): no lane calls tan.
 #pragma once
 #include <math.h>
 #include <stdint.h>
+
+#include "rp_overlap.h"
 
 #if defined(__HIPCC__)
 #define RPRJ_FN __host__ __device__ __forceinline__
@@ -187,10 +189,7 @@ inline const char* check_buffers(uint32_t width, uint32_t height, const void* de
   const Range in[7] = {{depth_cur, 8 * n},  {normal_cur, 24 * n}, {depth_prev, 8 * n}, {normal_prev, 24 * n},
                        {mean_prev, 24 * n}, {m2_prev, 24 * n},    {count_prev, 4 * n}};
   const Range out[4] = {{mean, 24 * n}, {m2, 24 * n}, {count, 4 * n}, {stats, 8 * (uint64_t)STATS_LEN}};
-  auto overlaps = [](const Range& a, const Range& b) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
-    return x < y + b.bytes && y < x + a.bytes;
-  };
+  auto overlaps = [](const Range& a, const Range& b) { return rpo::overlaps(a.p, a.bytes, b.p, b.bytes); };
   for (int o = 0; o < 4; o++) {
     for (int k = 0; k < 7; k++)
       if (overlaps(out[o], in[k])) return "an output must not alias an input (a gather: in place is wrong)";

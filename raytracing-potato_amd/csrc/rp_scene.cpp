@@ -39,7 +39,7 @@ constexpr uint32_t DEF_MAX_LEAF = 4, DEF_TRAV_THRESHOLD = 24, DEF_ALWAYS_MAX = 4
 constexpr double DEF_COST_TRAVERSE = 0.7;
 
 // to_srgb_u8's byte for one channel (utility.rs:212-216), in the host libm: the reference's arithmetic
-// (Rust's f64::powf is the platform pow).  Same expression as rph_to_srgb_u8 (rp_host.cpp).
+// (Rust's f64::powf is the platform pow).  Same expression as rph_to_srgb_u8 (rp_host_assets.cpp).
 uint32_t srgb_byte(double x) {
   if (x < 0.0) x = 0.0;
   if (x > 1.0) x = 1.0;

@@ -154,12 +154,8 @@ int rp_accum_tiles_select_device(const rp_render_params* p, const rp_error_param
   Tiling t;
   int rc = frame_tiling(p, t);
   if (rc) return rc;
-  if (t.shards != 1 || p->shard_map != RP_SHARD_INTERLEAVE)
-    return fail(RP_EINVAL, "the state is a whole frame's on one device: num_shards 0 or 1, shard 0, interleave");
   double tol, eps;
-  if (!rpa::resolve(e, tol, eps)) return fail(RP_EINVAL, "error params out of range (tol > 0; eps > 0 and finite)");
-  if (!(tile_share >= 0.0 && tile_share < 1.0)) return fail(RP_EINVAL, "tile_share must be in [0, 1)");
-  if (n_in > (uint32_t)rpk::TILE_SORT_MAX) return fail(RP_EINVAL, "n_in is above 16384 (rpk::TILE_SORT_MAX)");
+  if (const char* why = rpa::check_select(t.shards, p->shard_map, e, tile_share, n_in, tol, eps)) return fail(RP_EINVAL, why);
   const uint64_t list_bytes = 4ull * n_in;
   if (rpp::overlaps(d_tiles_out, list_bytes, d_tiles_in, list_bytes) || rpp::overlaps(d_tiles_out, list_bytes, d_over, list_bytes) ||
       rpp::overlaps(d_count, 4, d_tiles_out, list_bytes) || rpp::overlaps(d_count, 4, d_over, list_bytes))

@@ -2,7 +2,7 @@
 // next from the unit queues, and what a unit's batch number says about its frame, its samples and its RNG stream.
 //
 // The render kernel (rp_kernel.hip, through rp_device.h's DevEnv) and the host library's test hook (rp_host.h
-// rph_unit_walk, through rp_host.cpp's HostEnv) compile this one text, so tests/test_unit_queues.py walks the kernel's
+// rph_unit_walk, through rp_host_sched.cpp's HostEnv) compile this one text, so tests/test_unit_queues.py walks the kernel's
 // own queues on the CPU: every unit of every frame exactly once, at the right pixel.
 //
 // ---- queue order

@@ -3,8 +3,8 @@
 //
 // Every value is IEEE binary64, every expression is written in the operation order include/rp.h gives and compiled
 // without contraction (-ffp-contract=off), so the kernel (rp_variance.hip), the CPU loop behind rph_batch_variance
-// (rp_host.cpp) and the numpy model of the tests (tests/denoise_var_ref.py, written from the definition and not from
-// this file) agree to the last bit.
+// (rp_host_passes.cpp) and the numpy model of the tests (tests/denoise_var_ref.py, written from the definition and not
+// from this file) agree to the last bit.
 #pragma once
 #include <stdint.h>
 

@@ -120,6 +120,65 @@ def test_refusals():
         assert b"out of range" in H.rph_last_error()
 
 
+def _host_fold_as(tile, n_words, n_prior, n_frames, frames, stride, mean, m2, var):
+    """One set of rph_accum_frames arguments (arrays or None) through rph_accum_frames or (tile) through
+    rph_accum_frames_tiles as a one-block list -- n_listed = n_state_tiles = 1, tiles = [0], tile_words = n_words: the
+    return code and the message after the `rph_<name>: ` prefix."""
+    from rtpotato import _ffi as F
+    H = F.host()
+    p = lambda a: a.ctypes.data if a is not None else None
+    one = np.zeros(1, dtype=np.uint32)
+    if tile:
+        name = b"rph_accum_frames_tiles: "
+        rc = H.rph_accum_frames_tiles(n_words, 1, p(one), 1, n_prior, n_frames, p(frames), stride, p(mean), p(m2), p(var))
+    else:
+        name = b"rph_accum_frames: "
+        rc = H.rph_accum_frames(n_words, n_prior, n_frames, p(frames), stride, p(mean), p(m2), p(var))
+    msg = H.rph_last_error() if rc else name
+    assert msg.startswith(name) and one[0] == 0, msg
+    return rc, msg[len(name):]
+
+
+def test_plain_fold_is_the_tile_fold_with_one_block():
+    """rp_accum.h states the two folds' refusals once (check_fold) and the host folds them with one loop: the table of
+    test_refusals, and the state above 2^40 - 512 words, is refused by both with one message -- but for the block of no
+    words, where each names its own argument -- and accepted arguments give equal bits."""
+    from rtpotato import _ffi as F
+    fr = np.ones(40)
+    mean, m2, var = np.full(4, A.PAD), np.full(4, A.PAD), np.full(4, A.PAD)
+    ok = dict(n_words=4, n_prior=0, n_frames=3, frames=fr, stride=4, mean=mean, m2=m2, var=var)
+    for kw, want in (({"frames": None}, b"non-NULL"), ({"mean": None}, b"non-NULL"), ({"m2": None}, b"non-NULL"),
+                     ({"n_frames": 0}, b"n_frames is zero"), ({"n_words": 0}, (b"n_words is zero", b"tile_words is zero")),
+                     ({"stride": 3}, b"frame_stride is below"), ({"n_frames": 1}, b"at least two frames"),
+                     ({"n_prior": 2 ** 31 - 3}, b"2^31 - 1"), ({"n_prior": 2 ** 32 - 1}, b"2^31 - 1"),
+                     ({"n_words": 2 ** 40, "stride": 2 ** 40}, b"2^40 - 512"),
+                     ({"mean": fr[8:]}, b"alias the frames"), ({"m2": fr[11:]}, b"alias the frames"),
+                     ({"var": fr[1:]}, b"alias the frames"), ({"m2": mean}, b"alias one another"),
+                     ({"var": m2[1:]}, b"alias one another")):
+        (rc_a, msg_a), (rc_b, msg_b) = (_host_fold_as(tile, **{**ok, **kw}) for tile in (False, True))
+        assert rc_a == rc_b == F.RP_EINVAL, kw
+        if isinstance(want, tuple):
+            assert (msg_a, msg_b) == want, kw
+        else:
+            assert msg_a == msg_b and want in msg_a, (kw, msg_a, msg_b)
+    assert (fr == 1.0).all() and all((a == A.PAD).all() for a in (mean, m2, var))
+    rng = np.random.default_rng(SEED + 3)
+    for n_words in (1, 4, 5):
+        for n_prior in (0, 2):
+            for n_frames in (1, 5):
+                for stride in (n_words, n_words + 3):
+                    frames = A.synthetic(n_frames, n_words, stride, SEED + 10 * n_words + n_frames)
+                    state = rng.random((2, n_words))  # (read only with n_prior frames behind it)
+                    got = []
+                    for tile in (False, True):
+                        m, q = state[0].copy(), state[1].copy()
+                        v = np.full(n_words, A.PAD) if n_prior + n_frames >= 2 else None
+                        assert _host_fold_as(tile, n_words, n_prior, n_frames, frames, stride, m, q, v)[0] == F.RP_OK
+                        got.append((m, q, v))
+                    for a, b in zip(*got):
+                        assert (a is None and b is None) or A.same_bits(a, b), (n_words, n_prior, n_frames, stride)
+
+
 def test_error_params_struct(tmp_path):
     """sizeof and offsets of rp_error_params and RP_ERROR_STATS_LEN against a tiny C program."""
     from rtpotato import _ffi as F

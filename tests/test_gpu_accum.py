@@ -134,6 +134,40 @@ def test_frames_refusals(gpu):
     assert bool((fr[12:16] == 1.0).all()) and bool((out[1, :4] == 0.0).all()) and bool((out[2, :4] == 0.0).all())
 
 
+def test_frames_refusals_are_the_host_library_s(gpu):
+    """test_frames_refusals' table through both libraries, each on buffers of its own with the same layout (40 words of
+    frames, three 8-word outputs; a pointer is a buffer and an offset in words): rp_accum_frames_device's message is
+    rph_accum_frames' after its prefix -- rp_accum.h's check_fold, compiled into both -- and neither call writes."""
+    import torch
+    from rtpotato import _ffi as F
+    L, H = F.rp(), F.host()
+    dev = {"fr": torch.ones(40, dtype=torch.float64, device="cuda"),
+           "out": torch.full((3, 8), A.PAD, dtype=torch.float64, device="cuda")}
+    host = {"fr": np.ones(40), "out": np.full((3, 8), A.PAD)}
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    base = lambda bufs, name: bufs[name].data_ptr() if bufs is dev else bufs[name].ctypes.data
+    ok = dict(n_words=4, n_prior=0, n_frames=3, frames=("fr", 0), stride=4, mean=("out", 0), m2=("out", 8), var=("out", 16))
+
+    def call(bufs, **kw):
+        a = {**ok, **kw}
+        ptr = [None if a[k] is None else base(bufs, a[k][0]) + 8 * a[k][1] for k in ("frames", "mean", "m2", "var")]
+        if bufs is dev:
+            rc = L.rp_accum_frames_device(a["n_words"], a["n_prior"], a["n_frames"], ptr[0], a["stride"], *ptr[1:], s)
+            return rc, L.rp_last_error()
+        rc = H.rph_accum_frames(a["n_words"], a["n_prior"], a["n_frames"], ptr[0], a["stride"], *ptr[1:])
+        return rc, H.rph_last_error()
+
+    for kw in ({"frames": None}, {"mean": None}, {"m2": None}, {"n_frames": 0}, {"n_words": 0}, {"stride": 3},
+               {"n_frames": 1}, {"n_prior": 2 ** 31 - 3}, {"n_words": 2 ** 40, "stride": 2 ** 40}, {"mean": ("fr", 8)},
+               {"m2": ("fr", 11)}, {"var": ("fr", 1)}, {"m2": ("out", 0)}, {"var": ("out", 11)}):
+        (rc_d, msg_d), (rc_h, msg_h) = call(dev, **kw), call(host, **kw)
+        assert rc_d == rc_h == F.RP_EINVAL, kw
+        assert msg_h == b"rph_accum_frames: " + msg_d and msg_d, (kw, msg_d, msg_h)
+    torch.cuda.synchronize()
+    assert bool((dev["out"] == A.PAD).all()) and bool((dev["fr"] == 1.0).all())
+    assert (host["out"] == A.PAD).all() and (host["fr"] == 1.0).all()
+
+
 _chain: dict = {}
 
 

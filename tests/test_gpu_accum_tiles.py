@@ -303,7 +303,7 @@ def test_tile_fold_refusals(gpu):
 
     for kw, msg in ((dict(frames=None), "non-NULL"), (dict(mean=None), "non-NULL"), (dict(m2=None), "non-NULL"),
                     (dict(tile_words=0), "tile_words is zero"), (dict(n_frames=0), "n_frames is zero"),
-                    (dict(n_listed=5), "above n_state_tiles"), (dict(tl=None), "d_tiles must be non-NULL"),
+                    (dict(n_listed=5), "above n_state_tiles"), (dict(tl=None), "tiles must be non-NULL"),
                     (dict(stride=7), "frame_stride is below"), (dict(n_prior=0x7fffffff), "2^31 - 1"),
                     (dict(n_frames=1), "at least two frames"), (dict(tile_words=1 << 40), "2^40 - 512"),
                     (dict(n_state=1 << 31, tile_words=1 << 10, n_listed=1), "2^40 - 512"),

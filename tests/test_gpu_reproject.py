@@ -265,8 +265,8 @@ def test_refusals(gpu):
                     ({"var_one": float("inf")}, b"var_one"), ({"var_one": float("nan")}, b"var_one"),
                     ({"mean": p8(fr, 8)}, b"alias the frames"), ({"var": p8(fr, 1)}, b"alias the frames"),
                     ({"m2": p8(st[0])}, b"one another"), ({"var": p8(st[1], 3)}, b"one another"),
-                    ({"count": p8(fr, 3)}, b"d_count must not alias"), ({"count": p8(st[0], 5)}, b"d_count must not alias"),
-                    ({"count": p8(st[2])}, b"d_count must not alias")):
+                    ({"count": p8(fr, 3)}, b"count must not alias"), ({"count": p8(st[0], 5)}, b"count must not alias"),
+                    ({"count": p8(st[2])}, b"count must not alias")):
         assert fold(**kw) == F.RP_EINVAL, kw
         assert msg in L.rp_last_error(), (kw, L.rp_last_error())
     torch.cuda.synchronize()

@@ -1,6 +1,6 @@
 // san_driver.cpp -- native driver of the host code for the sanitizer builds ("Host ASan/UBSan build of the
 // C++ oracle").  Built by `make -C raytracing-potato_amd sanitize` with -fsanitize=thread (TSan) and with
-// -fsanitize=address,undefined, linked with the host library's sources (rp_host.cpp, rp_bvh.cpp) and the oracle
+// -fsanitize=address,undefined, linked with the host library's sources (rp_host_*.cpp, rp_bvh.cpp) and the oracle
 // (oracle/rp_oracle.c) directly -- no Python and no LD_PRELOAD between the sanitizer and the code.  It exercises:
 //   - the multi-threaded binned-SAH builder and its SAH-optimal / greedy 4-wide collapse at 1, 3, 8 and 16 threads
 //     (rph_bvh_tree_hash: the tree must not depend on the thread count) and the structural self-check, on a random
