@@ -160,6 +160,16 @@ int rph_prim_test(uint32_t kind, const double g[9], const double* rays, uint64_t
 int rph_material_head(const uint32_t fields[6], uint32_t packed[2], uint32_t unpacked[7]);
 int rph_scene_materials(const rp_scene_desc* desc, uint64_t cap, uint32_t* words, uint64_t* n_materials);
 
+/* Test hook: the per-primitive normals table (raytracing-potato_amd/csrc/rp_layout.h TriNormals) the host builder
+ * makes for desc beside its primitive records -- the table librp.so uploads for a host-built tree, and the statement
+ * (tri_normals_fill) the device builders' gather kernel compiles.  The tree is rph_bvh_tree_hash_opt's (node_format,
+ * always_max, always_minor).  For the first min(cap, n) of the n primitives in leaf order: normals gets 9 doubles
+ * {n0.xyz, n1.xyz, n2.xyz} (a sphere: zeros), refs 4 words {v0, v1, v2, src} (the PrimRef: global vertex ids, source
+ * hittable), kinds one word (0 sphere, 1 triangle); each of the three may be NULL.  *n_prims = n.  RP_EINVAL for a NULL
+ * desc or n_prims or a scene the builder refuses. */
+int rph_tri_normals(const rp_scene_desc* desc, uint32_t node_format, int32_t always_max, uint32_t always_minor, uint64_t cap,
+                    double* normals, uint32_t* refs, uint32_t* kinds, uint64_t* n_prims);
+
 /* Test hook: the render kernel's unit fetch, run on the CPU (raytracing-potato_amd/csrc/rp_units.h fetch_pixel, unit_frame
  * and unit_spp: the same header the kernel compiles, in a host environment that stands in for the kernarg segment, the
  * atomics and the wave).  The launch is planned by rps::plan_launch from the arguments rph_plan_launch takes (and must

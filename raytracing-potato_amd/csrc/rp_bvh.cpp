@@ -1040,8 +1040,12 @@ int build(const rp_scene_desc* d, const BuildOptions& opt, PackedScene& out, std
   // ---- primitives in leaf order (value-initialised: a scene without primitives keeps one zero record)
   out.prims.resize(order.size() ? order.size() : 1);
   out.prim_refs.resize(out.prims.size());
+  out.tri_nrm.resize(out.prims.size());
   parallel_for(order.size(), threads, [&](size_t b, size_t e) {
-    for (size_t k = b; k < e; k++) pack_prim(d, vbase, order[k], out.prims[k], out.prim_refs[k]);
+    for (size_t k = b; k < e; k++) {
+      pack_prim(d, vbase, order[k], out.prims[k], out.prim_refs[k]);
+      pack_tri_normals(d, order[k], out.tri_nrm[k]);
+    }
   });
   return RP_OK;
 }
@@ -1075,6 +1079,15 @@ static void pack_prim(const rp_scene_desc* d, const std::vector<uint64_t>& vbase
     pr.v[1] = (uint32_t)(vbase[h.mesh] + i1);
     pr.v[2] = (uint32_t)(vbase[h.mesh] + i2);
   }
+}
+
+void pack_tri_normals(const rp_scene_desc* d, uint32_t id, rpl::TriNormals& tn) {
+  const rp_hittable& h = d->hittables[id];
+  std::memset(&tn, 0, sizeof tn);
+  if (h.kind == RP_HITTABLE_SPHERE) return;
+  const rp_mesh& m = d->meshes[h.mesh];
+  // the mesh's own array at its own ids: the doubles the concatenated table holds at PrimRef::v (vbase + id)
+  rpl::tri_normals_fill(tn, m.normals, m.indices[h.triangle], m.indices[h.triangle + 1], m.indices[h.triangle + 2]);
 }
 
 int prim_input(const rp_scene_desc* d, PrimInput& out, std::string& err) {

@@ -56,6 +56,7 @@ struct PackedScene {
   std::vector<rpl::Node8Q> wnodes;    // NODES_W8: the 8-wide quantized tree (its own leaf order)
   std::vector<rpl::Prim> prims;       // leaf order
   std::vector<rpl::PrimRef> prim_refs;  // leaf order: vertex ids, source hittable
+  std::vector<rpl::TriNormals> tri_nrm; // leaf order: a triangle's three vertex normals (a sphere's entry: zeros)
   std::vector<double> vnrm;           // 3 per global vertex (mesh vertices concatenated)
   std::vector<double> vuv;            // 2 per global vertex
   std::vector<rpl::Material> materials;
@@ -112,6 +113,9 @@ struct PrimInput {
 };
 int prim_input(const rp_scene_desc* d, PrimInput& out, std::string& err);
 
+// The vertex normals of hittable `id` (a sphere: zeros): the record build() stores beside prims[k] and prim_refs[k].
+void pack_tri_normals(const rp_scene_desc* d, uint32_t id, rpl::TriNormals& tn);
+
 // Structural self-check of a packed tree: every primitive referenced exactly once, every child box
 // contains its subtree's primitive boxes, no cycles.  Returns RP_OK or RP_EINTERNAL (message in err).
 int check(const PackedScene& s, std::string& err);
@@ -126,6 +130,7 @@ struct GpuTree {
   uint32_t node_format = rpl::NODES_F32;
   rpl::Prim* d_prims = nullptr;   // leaf order
   rpl::PrimRef* d_prim_refs = nullptr;
+  rpl::TriNormals* d_tri_nrm = nullptr;  // leaf order, filled by gather_tri_normals
   uint64_t n_nodes = 0, n_leaves = 0;
   uint32_t max_depth = 0;
   double qbound = 0.0;
@@ -138,5 +143,11 @@ enum { GPU_LBVH = 0, GPU_PLOC = 1 };
 // align: PLOC's depth-first node families start at multiples of this many nodes (pad slots zero; RP_LAYOUT_DFS_LINE).
 int build_gpu(const rpb::PrimInput& in, uint32_t max_leaf, uint32_t node_format, uint32_t algo, double cost_traverse,
               uint32_t align, GpuTree& out, std::string& err);
+
+// The per-primitive normals of a device-built tree: out.d_tri_nrm = n records (one per primitive of out, leaf order)
+// gathered from d_vnrm, the meshes' normals concatenated on the device (3 doubles per global vertex, PrimRef::v's
+// numbering), by one kernel on the builds' stream, waited for.  RP_ENOMEM when the table cannot be allocated; on any
+// failure out.d_tri_nrm stays NULL.  The caller owns the table.
+int gather_tri_normals(GpuTree& out, uint64_t n, const double* d_vnrm, std::string& err);
 
 }  // namespace rpg

@@ -348,6 +348,20 @@ __global__ void permute_kernel(uint32_t n, const uint32_t* __restrict__ order, c
   refs[k] = refs_in[i];
 }
 
+// The per-primitive normals of a finished tree (rp_layout.h TriNormals): primitive k's three vertex normals from the
+// concatenated vertex table at its PrimRef's ids, zeros for a sphere -- the host builder's pack_tri_normals.
+__global__ void tri_normals_kernel(uint32_t n, const rpl::Prim* __restrict__ prims, const rpl::PrimRef* __restrict__ refs,
+                                   const double* __restrict__ vnrm, rpl::TriNormals* __restrict__ out) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  rpl::TriNormals t{};
+  if (prims[k].kind == rpl::PRIM_TRIANGLE) {
+    const rpl::PrimRef r = refs[k];
+    rpl::tri_normals_fill(t, vnrm, r.v[0], r.v[1], r.v[2]);
+  }
+  out[k] = t;
+}
+
 __global__ void order_kernel(uint32_t n, const uint64_t* __restrict__ keys, uint32_t* __restrict__ order) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n) order[k] = (uint32_t)keys[k];
@@ -858,6 +872,22 @@ int build_gpu(const rpb::PrimInput& in, uint32_t max_leaf, uint32_t node_format,
   out.d_nodes = o.nodes.release();
   out.d_prims = o.prims.release();
   out.d_prim_refs = o.refs.release();
+  return RP_OK;
+}
+
+int gather_tri_normals(GpuTree& out, uint64_t n, const double* d_vnrm, std::string& err) {
+  out.d_tri_nrm = nullptr;
+  if (!out.d_prims || !out.d_prim_refs || !d_vnrm || n == 0 || n > 0xFFFFFFFFull)
+    return failed(err, RP_EINVAL, "triangle normals: a built tree and the vertex normals are needed");
+  DevBuf<rpl::TriNormals> t;
+  hipError_t e = hipSuccess;
+  alloc(e, t, n);
+  if (e != hipSuccess) return alloc_failed("triangle normals", e, err);
+  launch(tri_normals_kernel, n, (uint32_t)n, out.d_prims, out.d_prim_refs, d_vnrm, t.get());
+  RPG_CHECK("triangle normals");
+  e = hipDeviceSynchronize();
+  RPG_CHECK("triangle normals");
+  out.d_tri_nrm = t.release();
   return RP_OK;
 }
 

@@ -1127,6 +1127,19 @@ RPK_INLINE void traverse(const KScene& S, lds_u32* stk, uint32_t stride, V3 o, V
   hr.km = t.bestm;
 }
 
+// A word of a material, texture or per-primitive normals record: 32-bit byte offset from the wave-uniform table base
+// (scalar-base + vector-offset loads, as nodes and primitives are read; the builder refuses tables beyond 4 GB).
+template <class T>
+RPK_INLINE T rec_load(const void* base, uint32_t off) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
+}
+// Two doubles of such a record as one 16 B load from an address that is 8-byte aligned only (rpl::TriNormals).  Its own
+// function: as a template argument the typedef would lose its alignment.
+typedef double double2a8 __attribute__((ext_vector_type(2), aligned(8)));
+RPK_INLINE double2a8 rec_load_d2(const void* base, uint32_t off) {
+  return *reinterpret_cast<const double2a8*>(reinterpret_cast<const char*>(base) + off);
+}
+
 // Hit record of the closest primitive (hittable.rs:59-62, 103-107).
 struct Surf {
   V3 p, n;
@@ -1152,13 +1165,22 @@ RPK_INLINE bool surface_at(const KScene& S, const HitRec& hr, V3 o, V3 d, Surf& 
   s.v = 0.0;
   if (known ? (hr.km & KM_TRIANGLE) != 0 : p->kind == rpl::PRIM_TRIANGLE) {
     const double u = hr.u, v = hr.v, w = 1.0 - u - v;
-    const rpl::PrimRef& pr = S.prim_refs[hr.prim];
-    const uint32_t i0 = pr.v[0], i1 = pr.v[1], i2 = pr.v[2];
-    const V3 n0 = v3(S.vnrm[3 * i0], S.vnrm[3 * i0 + 1], S.vnrm[3 * i0 + 2]);
-    const V3 n1 = v3(S.vnrm[3 * i1], S.vnrm[3 * i1 + 1], S.vnrm[3 * i1 + 2]);
-    const V3 n2 = v3(S.vnrm[3 * i2], S.vnrm[3 * i2 + 1], S.vnrm[3 * i2 + 2]);
+    // The three vertex normals: the primitive's own 72 B record (rp_layout.h TriNormals), five loads at a 32-bit byte
+    // offset from the wave-uniform table base that depend on the hit record alone -- in shade_ray they go out with the
+    // material head's, and shading waits for memory once in front of the interpolation.  (Through the vertex ids they
+    // were two round trips: PrimRef, then nine loads from three rows of the vertex table.)
+    const uint32_t toff = (uint32_t)hr.prim * (uint32_t)sizeof(rpl::TriNormals);
+    const double2a8 q0 = rec_load_d2(S.tri_nrm, toff), q1 = rec_load_d2(S.tri_nrm, toff + 16u);
+    const double2a8 q2 = rec_load_d2(S.tri_nrm, toff + 32u), q3 = rec_load_d2(S.tri_nrm, toff + 48u);
+    const double q4 = rec_load<double>(S.tri_nrm, toff + 64u);
+    // (all 18 words count as read here, where they are issued: the compiler neither splits the group nor sinks a part
+    // of it behind a wait of its own)
+    asm volatile("" : : "v"(q0.x), "v"(q0.y), "v"(q1.x), "v"(q1.y), "v"(q2.x), "v"(q2.y), "v"(q3.x), "v"(q3.y), "v"(q4));
+    const V3 n0 = v3(q0.x, q0.y, q1.x), n1 = v3(q1.y, q2.x, q2.y), n2 = v3(q3.x, q3.y, q4);
     s.n = add(add(smul(w, n0), smul(u, n1)), smul(v, n2));
-    if (need_uv()) {
+    if (need_uv()) {  // a textured mesh (rare): the ids, then the uvs -- two trips
+      const rpl::PrimRef& pr = S.prim_refs[hr.prim];
+      const uint32_t i0 = pr.v[0], i1 = pr.v[1], i2 = pr.v[2];
       s.u = (w * S.vuv[2 * i0] + u * S.vuv[2 * i1]) + v * S.vuv[2 * i2];
       s.v = (w * S.vuv[2 * i0 + 1] + u * S.vuv[2 * i1 + 1]) + v * S.vuv[2 * i2 + 1];
     }
@@ -1177,12 +1199,6 @@ RPK_INLINE bool surface(const KScene& S, const HitRec& hr, V3 o, V3 d, Surf& s, 
 
 // ------------------------------------------------------------------ shading ----------------------
 
-// A word of a material or texture record: 32-bit byte offset from the wave-uniform table base (scalar-base +
-// vector-offset loads, as nodes and primitives are read; the builder refuses tables beyond 4 GB).
-template <class T>
-RPK_INLINE T rec_load(const void* base, uint32_t off) {
-  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + off);
-}
 RPK_INLINE uint32_t mat_at(uint32_t material) { return material * (uint32_t)sizeof(rpl::Material); }
 
 // x / 255.0 for a byte x, correctly rounded without a division: q0 = x * fl(1/255) is off by at most
@@ -1526,7 +1542,7 @@ RPK_INLINE KScene load_scene(KArgsPtr A) {
   S.nodes = A->S.nodes;
   S.prims = A->S.prims;
   S.prim_refs = A->S.prim_refs;
-  S.vnrm = A->S.vnrm;
+  S.tri_nrm = A->S.tri_nrm;
   S.vuv = A->S.vuv;
   S.mats = A->S.mats;
   S.texs = A->S.texs;

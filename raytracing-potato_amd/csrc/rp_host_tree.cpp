@@ -247,6 +247,22 @@ int rph_bvh_tree_hash_opt(const rp_scene_desc* desc, uint32_t node_format, uint3
   return RP_OK;
 }
 
+int rph_tri_normals(const rp_scene_desc* desc, uint32_t node_format, int32_t always_max, uint32_t always_minor, uint64_t cap,
+                    double* normals, uint32_t* refs, uint32_t* kinds, uint64_t* n_prims) {
+  if (!desc || !n_prims) return fail("rph_tri_normals: non-NULL pointers");
+  rpb::PackedScene ps;
+  if (const int rc = build_tree(desc, node_format, RP_COLLAPSE_AUTO, 0, always_max, always_minor, ps)) return rc;
+  static_assert(sizeof(rpl::TriNormals) == 9 * sizeof(double) && sizeof(rpl::PrimRef) == 4 * sizeof(uint32_t), "rows");
+  const uint64_t n = desc->n_hittables;  // the packed tables hold one record more for a scene without primitives
+  *n_prims = n;
+  for (uint64_t k = 0; k < n && k < cap; k++) {
+    if (normals) std::memcpy(normals + 9 * k, &ps.tri_nrm[k], sizeof(rpl::TriNormals));
+    if (refs) std::memcpy(refs + 4 * k, &ps.prim_refs[k], sizeof(rpl::PrimRef));
+    if (kinds) kinds[k] = ps.prims[k].kind;
+  }
+  return RP_OK;
+}
+
 int rph_material_head(const uint32_t fields[6], uint32_t packed[2], uint32_t unpacked[7]) {
   if (!fields || !packed || !unpacked) return fail("rph_material_head: non-NULL pointers");
   rpl::Material m{};

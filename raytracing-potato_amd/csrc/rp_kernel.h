@@ -10,7 +10,7 @@ struct KScene {
   const void* nodes;     // rpl::Node4 or rpl::Node4Q records (node_format)
   const rpl::Prim* prims;
   const rpl::PrimRef* prim_refs;
-  const double* vnrm;
+  const rpl::TriNormals* tri_nrm;  // per primitive (leaf order, beside prims and prim_refs)
   const double* vuv;
   const rpl::Material* mats;
   const rpl::Texture* texs;

@@ -190,6 +190,27 @@ struct alignas(16) PrimRef {
 };
 static_assert(sizeof(PrimRef) == 16, "PrimRef must be 16 B");
 
+// Per primitive, read only for the closest hit on a triangle: the three vertex normals, the doubles of the meshes'
+// normal arrays at PrimRef::v[0..2] copied (never recomputed), so shading reads one contiguous 72 B run at the
+// primitive's index instead of the ids and then three rows of a vertex table.  A sphere's entry is zeros, unread.
+// 8-byte aligned, not 16: the kernel reads it as four 16 B loads and one 8 B load at offsets 0, 16, 32, 48, 64
+// (rp_device.h surface_at), which global memory serves at any 4-byte alignment.
+struct TriNormals {
+  double n[3][3];  // n[j] = the normal of vertex j
+};
+static_assert(sizeof(TriNormals) == 72 && alignof(TriNormals) == 8, "TriNormals must be 72 B, 8-byte aligned");
+static_assert(offsetof(TriNormals, n) == 0 && sizeof(double[3]) == 24, "TriNormals: n0 at 0, n1 at 24, n2 at 48");
+// a table of as many records as the primitive table stays within its 32-bit byte offsets (rp_bvh.cpp prim_input, build)
+static_assert(sizeof(TriNormals) <= sizeof(Prim), "TriNormals offsets are covered by the primitive table's limit");
+// The record of one triangle from the (concatenated or per-mesh) normal array `nrm` and its three vertex ids: the one
+// statement the host builder and the device gather share.
+template <class I>
+RPL_HD inline void tri_normals_fill(TriNormals& t, const double* nrm, I i0, I i1, I i2) {
+  const I id[3] = {i0, i1, i2};
+  for (int j = 0; j < 3; j++)
+    for (int c = 0; c < 3; c++) t.n[j][c] = nrm[3 * (size_t)id[j] + c];
+}
+
 // Material: rp_material flattened (material.rs:87-91).
 //
 // head, head_tex (offsets 24, 28: one 8 B load beside scatter_param) repeat the six control words for the render

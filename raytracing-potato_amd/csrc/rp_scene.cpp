@@ -192,6 +192,20 @@ int scene_create(const rp_scene_desc* desc, int device, const rp_scene_options* 
     s->d_nodes.adopt(static_cast<uint8_t*>(gt.d_nodes), rp_node_bytes(node_format) * n_tree_nodes);
     s->d_prims.adopt(gt.d_prims, n_tree_prims);
     s->d_prim_refs.adopt(gt.d_prim_refs, n_tree_prims);
+    // the per-primitive normals: the meshes' normals go up mesh after mesh, one gather fills the table (leaf order is
+    // known only now), and the vertex table is freed again -- no kernel reads it
+    {
+      DevBuf<double> d_vnrm;
+      uint64_t n_vert = 0;
+      for (uint32_t i = 0; i < desc->n_meshes; i++) n_vert += desc->meshes[i].n_vertices;
+      if (!d_vnrm.alloc(3 * n_vert + 3)) return fail(RP_ENOMEM, "hipMalloc vertex normals");
+      for (uint64_t i = 0, vb = 0; i < desc->n_meshes; vb += desc->meshes[i].n_vertices, i++) {
+        const rp_mesh& m = desc->meshes[i];
+        if (m.n_vertices) RP_HIP(hipMemcpy(d_vnrm.get() + 3 * vb, m.normals, sizeof(double) * 3 * m.n_vertices, hipMemcpyHostToDevice));
+      }
+      if ((rc = rpg::gather_tri_normals(gt, n_tree_prims, d_vnrm.get(), err))) return fail(rc, err);
+      s->d_tri_nrm.adopt(gt.d_tri_nrm, n_tree_prims);
+    }
     ps.root = 0;
     ps.max_depth = gt.max_depth;
     ps.n_leaves = gt.n_leaves;
@@ -223,19 +237,20 @@ int scene_create(const rp_scene_desc* desc, int device, const rp_scene_options* 
   } else if ((rc = node_format == rpl::NODES_W8   ? upload(ps.wnodes, s->d_nodes)
                    : node_format == rpl::NODES_Q8 ? upload(ps.qnodes, s->d_nodes)
                                                   : upload(ps.nodes, s->d_nodes)) ||
-             (rc = upload(ps.prims, s->d_prims)) || (rc = upload(ps.prim_refs, s->d_prim_refs))) {
+             (rc = upload(ps.prims, s->d_prims)) || (rc = upload(ps.prim_refs, s->d_prim_refs)) ||
+             (rc = upload(ps.tri_nrm, s->d_tri_nrm))) {
     return rc;
   }
   phase[3] = lap();  // the device build, or the host tree's upload
-  // vertex normals and uvs (read at a closest hit), mesh after mesh from the caller's arrays: no host copy
+  // vertex uvs (read at a closest hit on a textured mesh), mesh after mesh from the caller's arrays: no host copy.  The
+  // vertex normals are on the device per primitive only (d_tri_nrm, above).
   uint64_t n_vert = 0;
   for (uint32_t i = 0; i < desc->n_meshes; i++) n_vert += desc->meshes[i].n_vertices;
-  if (!s->d_vnrm.alloc(3 * n_vert + 3) || !s->d_vuv.alloc(2 * n_vert + 2)) return fail(RP_ENOMEM, "hipMalloc vertex tables");
+  if (!s->d_vuv.alloc(2 * n_vert + 2)) return fail(RP_ENOMEM, "hipMalloc vertex tables");
   for (uint64_t i = 0, vb = 0; i < desc->n_meshes; vb += desc->meshes[i].n_vertices, i++) {
     const rp_mesh& m = desc->meshes[i];
     if (!m.n_vertices) continue;
-    if (hipMemcpy(s->d_vnrm.get() + 3 * vb, m.normals, sizeof(double) * 3 * m.n_vertices, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(s->d_vuv.get() + 2 * vb, m.uvs, sizeof(double) * 2 * m.n_vertices, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(s->d_vuv.get() + 2 * vb, m.uvs, sizeof(double) * 2 * m.n_vertices, hipMemcpyHostToDevice) != hipSuccess)
       return fail(RP_EHIP, "vertex table upload");
   }
   if ((rc = upload(ps.materials, s->d_mats)) || (rc = upload(ps.textures, s->d_texs)) || (rc = upload(ps.texels, s->d_texels)))
@@ -244,7 +259,7 @@ int scene_create(const rp_scene_desc* desc, int device, const rp_scene_options* 
     return fail(RP_ENOMEM, "hipMalloc diagnostics");
   s->ks.diag = s->d_diag.get();
   s->ks.nodes = s->d_nodes.get(), s->ks.prims = s->d_prims.get(), s->ks.prim_refs = s->d_prim_refs.get();
-  s->ks.vnrm = s->d_vnrm.get(), s->ks.vuv = s->d_vuv.get();
+  s->ks.tri_nrm = s->d_tri_nrm.get(), s->ks.vuv = s->d_vuv.get();
   s->ks.mats = s->d_mats.get(), s->ks.texs = s->d_texs.get(), s->ks.texels = s->d_texels.get();
   s->ks.background = ps.background;
   s->ks.root = ps.root;
@@ -266,8 +281,8 @@ int scene_create(const rp_scene_desc* desc, int device, const rp_scene_options* 
   s->n_leaves = ps.n_leaves;
   s->n_prims = desc->n_hittables;
   s->max_depth = ps.max_depth;
-  s->device_bytes = rp_node_bytes(node_format) * n_tree_nodes + (sizeof(rpl::Prim) + sizeof(rpl::PrimRef)) * n_tree_prims +
-                    sizeof(double) * 5 * n_vert + sizeof(rpl::Material) * ps.materials.size() +
+  s->device_bytes = rp_node_bytes(node_format) * n_tree_nodes + (sizeof(rpl::Prim) + sizeof(rpl::PrimRef) + sizeof(rpl::TriNormals)) * n_tree_prims +
+                    sizeof(double) * 2 * n_vert + sizeof(rpl::Material) * ps.materials.size() +
                     sizeof(rpl::Texture) * ps.textures.size() + sizeof(uint32_t) * ps.texels.size();
   // Cost-ordered tiles for every scene: cache-resident scenes (C3: 11 MB) gain ~15 % from them (short frame tail);
   // past the 256 MB Infinity Cache (C5: 2.5 GB) the Z-order once won (one device-wide queue: cost order scattered the

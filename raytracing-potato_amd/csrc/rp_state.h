@@ -87,7 +87,8 @@ struct rp_scene {
   DevBuf<uint8_t> d_nodes;  // rpl::Node4, Node4Q or Node8Q records (ks.node_format), in bytes
   DevBuf<rpl::Prim> d_prims;
   DevBuf<rpl::PrimRef> d_prim_refs;
-  DevBuf<double> d_vnrm, d_vuv;
+  DevBuf<rpl::TriNormals> d_tri_nrm;  // per primitive: a triangle's vertex normals (the vertex normals' only copy)
+  DevBuf<double> d_vuv;
   DevBuf<rpl::Material> d_mats;
   DevBuf<rpl::Texture> d_texs;
   DevBuf<uint32_t> d_texels;

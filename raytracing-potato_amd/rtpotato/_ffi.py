@@ -216,7 +216,7 @@ HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
                 "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
                 "rph_tiles_unit_walk", "rph_material_head", "rph_scene_materials", "rph_reproject",
-                "rph_accum_frames_counts", "rph_draw_values"]
+                "rph_accum_frames_counts", "rph_draw_values", "rph_tri_normals"]
 
 
 def rp_lib_path() -> str:
@@ -402,6 +402,8 @@ def host() -> ctypes.CDLL:
                                         POINTER(c_uint64), c_void_p, c_void_p]
     lib.rph_material_head.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.rph_scene_materials.argtypes = [POINTER(rp_scene_desc), c_uint64, c_void_p, POINTER(c_uint64)]
+    lib.rph_tri_normals.argtypes = [POINTER(rp_scene_desc), c_uint32, ctypes.c_int32, c_uint32, c_uint64, c_void_p, c_void_p,
+                                    c_void_p, POINTER(c_uint64)]
     lib.rph_reproject.argtypes = [POINTER(rp_reproject_params), c_uint32, c_uint32, POINTER(rp_camera),
                                   POINTER(rp_camera)] + [c_void_p] * 11
     lib.rph_accum_frames_counts.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
