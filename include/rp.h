@@ -17,7 +17,8 @@
  *   - Every function returning int returns RP_OK (0) or a negative rp_status; rp_last_error() gives a
  *     thread-local message for the last failure on the calling thread.  Nothing aborts or panics.
  *   - Ownership: the caller owns every buffer it passes.  rp_scene_create deep-copies the scene into
- *     device memory (HBM); the scene is immutable afterwards.
+ *     device memory (HBM); afterwards only a refit (rp_scene_refit_device, below) changes it: the geometry
+ *     moves, everything else stays.
  *   - Determinism (the RNG contract): the samples of pixel (i, j) are drawn in batches of
  *     N = params.samples_per_stream (0 -> RP_SAMPLES_PER_STREAM = 32); batch b (samples N*b .. N*b+N-1)
  *     is rendered with its own StdRng::seed_from_u64(params.seed + b*width*height + j*width + i)
@@ -888,6 +889,56 @@ int rp_render_multi(rp_multi* multi, const rp_camera* camera, const rp_render_pa
  * without it still serves every other call. */
 int rp_scene_tree(const rp_scene* scene, void* nodes, uint64_t node_bytes, void* prims, uint64_t prim_bytes,
                   void* prim_refs, uint64_t ref_bytes, uint32_t* node_format, uint32_t* root);
+
+/* ---------------------------------------------------------------- moving geometry: refit in place -- */
+/* New vertex positions, vertex normals and sphere records for a scene, without building it again: the primitive
+ * records, the per-primitive normals and the boxes of the EXISTING tree are rewritten on the device.  The topology is
+ * kept -- which primitives share a leaf, the entries, the node order, RP_LAYOUT_DFS_LINE's pad records, the stack depth
+ * -- and so are materials, textures, uvs, workspaces and everything they have learned (tile costs, unit orders, plans:
+ * results never depend on them).  A refit node stores exactly the boxes the builders would store for the same tree over
+ * the new geometry, so a refit with unchanged geometry changes no byte.  What a refit does not keep is
+ * the tree's QUALITY: the tree was chosen for the old geometry, and the further the geometry moves, the more node visits
+ * a ray costs compared with a fresh build (profiles/r32/refit_time.json).  Images stay exact.
+ *
+ * rp_refit_create (synchronous, allocates): the plan of a scene's tree -- its reachable nodes by level -- and 48 bytes
+ * of scratch per primitive and per node record.  RP_EINVAL: a NULL scene; an RP_NODES_W8 scene (a Node8Q slot encodes
+ * where a child lies relative to its node's centre, which moved geometry invalidates: rebuild such scenes); coord_max
+ * negative, not finite or above 2^54.  The handle belongs to the scene: destroy it before the scene.  An rp_multi has
+ * no accessor for its per-device scenes and cannot be refit.
+ *
+ * The coordinate bound B = max(coord_max, the largest |coordinate| of the scene's primitive boxes at create time, taken
+ * from the records with a few ulps of slack; coord_max = 0 keeps the build's bound) holds for all later updates.  The
+ * quantized traversal (RP_NODES_Q8) takes its slab slack from a bound on every node frame; create raises the scene's to
+ * cover B.  That only widens a conservative box test: no image changes, with or without an update, and
+ * rp_refit_destroy leaves the widened bound in place.  A render captured in a graph before the create keeps the bound
+ * it was captured with.
+ *
+ * rp_scene_refit_device: asynchronous on `stream` on the scene's device; it never allocates or synchronises and may be
+ * captured in a graph.  d_positions, d_normals: 3 doubles per global vertex -- the meshes' vertices concatenated in mesh
+ * order (rp_refit_info's n_vertices of them); d_spheres: 4 doubles {center.xyz, radius} per sphere, the sphere hittables
+ * numbered in hittable order (n_spheres of them).  Each is nullable and means "unchanged"; all three NULL is RP_EINVAL.
+ * d_normals alone rewrites only the per-primitive normals.  An update of the geometry names ALL of it -- d_positions
+ * when the scene has triangles, d_spheres when it has spheres, else RP_EINVAL: the handle keeps no copy of the current
+ * positions to complete a partial update from (DeviceScene.geometry() is the starting point of a deformation).
+ * d_status (required, one word, zeroed on the stream first) receives RP_REFIT_OUT_OF_BOUND when a primitive's box has a
+ * finite coordinate beyond B.  After an RP_NODES_Q8 refit that reported it, the scene's images are unspecified until a
+ * refit within the bound; RP_NODES_F32 scenes are unaffected by the bound.  In neither case can a traversal leave the
+ * buffers: the topology is untouched.  NaN coordinates behave as in the builders (never hit, nothing repaired).
+ * The caller orders a refit against renders, feature passes and queries of the same scene with streams and events: a
+ * refit while a render of the scene is in flight is a race.  The host's scene description is not involved.
+ *
+ * rp_scene_refit: the same from host buffers, synchronous; seconds (nullable) = device time of the kernels.
+ * Reprojecting the history of MOVING surfaces (rp_reproject_device) needs motion vectors and is not part of this.
+ * Added without an ABI bump: a library without these calls still serves every other call. */
+#define RP_REFIT_OUT_OF_BOUND 1u
+typedef struct rp_refit rp_refit;   /* opaque: a scene's refit plan and scratch */
+int rp_refit_create(rp_scene* scene, double coord_max, rp_refit** out);
+void rp_refit_destroy(rp_refit* refit);
+int rp_refit_info(const rp_refit* refit, uint64_t* n_vertices, uint64_t* n_spheres, uint32_t* n_levels, double* bound);
+int rp_scene_refit_device(rp_refit* refit, const double* d_positions, const double* d_normals, const double* d_spheres,
+                          uint32_t* d_status, void* stream);
+int rp_scene_refit(rp_refit* refit, const double* positions, const double* normals, const double* spheres,
+                   uint32_t* status, double* seconds);
 
 #ifdef __cplusplus
 }

@@ -266,6 +266,33 @@ int rph_tiles_unit_walk(uint32_t width, uint32_t height, uint32_t spp, uint32_t 
                         uint32_t n_blocks, uint32_t* units, uint64_t units_cap, uint64_t* n_units, uint32_t* queue_words,
                         uint32_t* entries);
 
+/* The CPU model of the refit (include/rp.h rp_scene_refit_device; raytracing-potato_amd/csrc/rp_refit.h, the header
+ * the device kernels compile): the plan, the primitive pass and the levels, in place on records laid out as
+ * rp_scene_tree returns them -- nodes: n_nodes Node4 (RP_NODES_F32) or Node4Q (RP_NODES_Q8) records, pads included;
+ * prims (80 B each) and refs (16 B each): n_prims of each in leaf order, the always-tested tail included; tri_normals
+ * (72 B each, nullable unless normals are given): the per-primitive normals.  positions, normals (3 doubles per vertex,
+ * n_vertices of them) and spheres (4 doubles each, n_spheres of them) as rp_scene_refit_device takes them, each nullable;
+ * bound: the coordinate bound B; status: one word, RP_REFIT_OUT_OF_BOUND or 0.  RP_EINVAL: the device's refusals
+ * (RP_NODES_W8, all inputs NULL, geometry named in part, a NULL status), and -- what the device cannot see -- fewer
+ * vertices than the triangles name, or a sphere count that is not the scene's; records that are no tree (an index out of
+ * range, a node reached twice).  Nothing is written by a refused call. */
+int rph_refit_records(uint32_t node_format, void* nodes, uint64_t n_nodes, uint32_t root, void* prims, const void* refs,
+                      void* tri_normals, uint64_t n_prims, const double* positions, const double* normals,
+                      const double* spheres, uint64_t n_vertices, uint64_t n_spheres, double bound, uint32_t* status);
+/* The plan alone: levels_out (nullable, n_nodes words) a node's level -- 0 without inner children, else 1 + the highest
+ * among them; 0xFFFFFFFF for a record that is not reachable from root (a pad) --, order_out (nullable, n_nodes words)
+ * the reachable nodes sorted by (level, index), then 0xFFFFFFFF, and *n_levels the number of levels. */
+int rph_refit_plan(uint32_t node_format, const void* nodes, uint64_t n_nodes, uint32_t root, uint32_t* levels_out,
+                   uint32_t* order_out, uint32_t* n_levels);
+/* The host builder's own tree of `before` (node_format, always_max, always_minor as rph_bvh_selfcheck_opt) refit to the
+ * geometry of `after` -- the same hittables over the same meshes' triangles, only positions, normals, centres and radii
+ * may differ (else RP_EINVAL) -- with the bound of both geometries, then held to the builder's check() against the
+ * after-geometry: RP_EINTERNAL with check's message when the refit tree fails it.  hashes (nullable, 2 values): FNV-1a
+ * of the node, primitive, reference and normal records before and after the refit (equal when after == before);
+ * status: the refit's status word. */
+int rph_bvh_refit_check(const rp_scene_desc* before, const rp_scene_desc* after, uint32_t node_format, int32_t always_max,
+                        uint32_t always_minor, uint64_t* hashes, uint32_t* status);
+
 const char* rph_last_error(void);
 
 #ifdef __cplusplus

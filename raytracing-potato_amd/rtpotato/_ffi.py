@@ -41,6 +41,7 @@ RP_MAX_FRAMES = 64
 RP_ERROR_STATS_LEN = 4  # rp_accum_error_device_ws: pixels counted, pixels over, bits of the largest finite e2, non-finite
 RP_REPROJECT_STATS_LEN = 4  # rp_reproject_device: pixels, pixels with count >= 1, the sum of the counts, off pixels
 RP_FRAME_ORDER_AUTO, RP_FRAME_ORDER_SEQUENTIAL, RP_FRAME_ORDER_INTERLEAVED, RP_FRAME_ORDER_PIXEL = 0, 1, 2, 3
+RP_REFIT_OUT_OF_BOUND = 1  # rp_scene_refit_device's status word: a primitive's box beyond the coordinate bound
 
 
 class rp_hittable(Structure):
@@ -167,6 +168,11 @@ def prim_dtype():
                      "offsets": [0, 72, 76], "itemsize": 80})
 
 
+def tri_normals_dtype():
+    import numpy as np
+    return np.dtype({"names": ["n"], "formats": [("<f8", (3, 3))], "offsets": [0], "itemsize": 72})
+
+
 def prim_ref_dtype():
     import numpy as np
     return np.dtype({"names": ["v", "src"], "formats": [("<u4", (3,)), "<u4"], "offsets": [0, 12], "itemsize": 16})
@@ -200,7 +206,8 @@ RP_SYMBOLS = ["rp_abi_version", "rp_last_error", "rp_device_count", "rp_scene_cr
               "rp_denoise_var_scratch_bytes", "rp_denoise_var_device", "rp_denoise_var", "rp_accum_frames_device",
               "rp_accum_error_device_ws", "rp_render_tiles_device_ws", "rp_accum_tiles_select_device",
               "rp_accum_frames_tiles_device", "rp_scene_tree", "rp_reproject_params_init", "rp_reproject_device",
-              "rp_reproject", "rp_accum_frames_counts_device"]
+              "rp_reproject", "rp_accum_frames_counts_device", "rp_refit_create", "rp_refit_destroy", "rp_refit_info",
+              "rp_scene_refit_device", "rp_scene_refit"]
 class rph_launch_plan(Structure):  # include/rp_host.h (test hook rph_plan_launch)
     _fields_ = [("n_shard_tiles", c_uint32), ("nbatch", c_uint32), ("plan_block", c_uint32), ("n_slots", c_uint64),
                 ("gather_stride", c_uint64), ("block_words", c_uint64), ("queue_groups", c_uint32),
@@ -216,7 +223,8 @@ HOST_SYMBOLS = ["rph_obj_load", "rph_mesh_free", "rph_tga_load", "rph_tga_save",
                 "rph_unit_walk", "rph_denoise", "rph_denoise_var", "rph_batch_variance", "rph_accum_frames",
                 "rph_accum_error", "rph_accum_frames_tiles", "rph_accum_tiles_select", "rph_plan_tiles_launch",
                 "rph_tiles_unit_walk", "rph_material_head", "rph_scene_materials", "rph_reproject",
-                "rph_accum_frames_counts", "rph_draw_values", "rph_tri_normals"]
+                "rph_accum_frames_counts", "rph_draw_values", "rph_tri_normals", "rph_refit_records", "rph_refit_plan",
+                "rph_bvh_refit_check"]
 
 
 def rp_lib_path() -> str:
@@ -340,6 +348,13 @@ def rp() -> ctypes.CDLL:
                                  POINTER(rp_camera)] + [c_void_p] * 11 + [POINTER(c_double)]
     lib.rp_accum_frames_counts_device.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p,
                                                   c_void_p, c_void_p, c_double, c_void_p]
+    if hasattr(lib, "rp_refit_create"):  # added without an ABI bump: an older library serves every other call
+        lib.rp_refit_create.argtypes = [c_void_p, c_double, POINTER(c_void_p)]
+        lib.rp_refit_destroy.argtypes = [c_void_p]
+        lib.rp_refit_destroy.restype = None
+        lib.rp_refit_info.argtypes = [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32), POINTER(c_double)]
+        lib.rp_scene_refit_device.argtypes = [c_void_p] * 6
+        lib.rp_scene_refit.argtypes = [c_void_p] * 5 + [POINTER(c_double)]
     if lib.rp_abi_version() != RP_ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.rp_abi_version()}, bindings expect {RP_ABI_VERSION} (rebuild)")
     _rp = lib
@@ -408,6 +423,11 @@ def host() -> ctypes.CDLL:
                                   POINTER(rp_camera)] + [c_void_p] * 11
     lib.rph_accum_frames_counts.argtypes = [c_uint64, c_uint32, c_uint32, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_double]
+    lib.rph_refit_records.argtypes = [c_uint32, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64,
+                                      c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_double, POINTER(c_uint32)]
+    lib.rph_refit_plan.argtypes = [c_uint32, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, POINTER(c_uint32)]
+    lib.rph_bvh_refit_check.argtypes = [POINTER(rp_scene_desc), POINTER(rp_scene_desc), c_uint32, ctypes.c_int32, c_uint32,
+                                        c_void_p, POINTER(c_uint32)]
     _host = lib
     return lib
 

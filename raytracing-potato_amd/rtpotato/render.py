@@ -151,6 +151,20 @@ class DeviceScene:
                                      refs.ctypes.data, refs.nbytes, None, None))
         return {"node_format": fmt.value, "root": root.value, "nodes": nodes, "prims": prims, "prim_refs": refs}
 
+    def geometry(self) -> dict:
+        """The geometry a refit moves, in rp_scene_refit_device's numbering, from the host scene (copies): "positions"
+        and "normals" (n_vertices, 3) -- the meshes' vertices concatenated in mesh order --, "spheres" (n_spheres, 4)
+        {center, radius} -- the sphere hittables in hittable order.  The starting point of a deformation."""
+        return scene_geometry(self.scene)
+
+    def refit_handle(self, coord_max: float = 0.0) -> "Refit":
+        """rp_refit_create: the plan and scratch that move this scene's geometry without building it again.  coord_max:
+        the largest |coordinate| later updates may reach (0 keeps the build's bound).  `self.scene`, the host
+        description, is never updated by a refit: it stays what the scene was created from."""
+        r = Refit(self, coord_max)
+        self.__dict__.setdefault("_refits", []).append(r)
+        return r
+
     def build_times(self) -> dict:
         """rp_scene_build_times: host seconds of the scene_create phases."""
         t = np.zeros(6)
@@ -159,7 +173,7 @@ class DeviceScene:
                          "workspace"), t.round(4).tolist()))
 
     def close(self) -> None:
-        for w in list(getattr(self, "_workspaces", ())):
+        for w in list(getattr(self, "_workspaces", ())) + list(getattr(self, "_refits", ())):
             w.close()
         if getattr(self, "handle", None):
             F.rp().rp_scene_destroy(self.handle)
@@ -736,6 +750,124 @@ class DeviceScene:
         mats = np.empty(len(r), dtype=np.uint32)
         F.check(F.rp().rp_intersect(self.handle, r.ctypes.data, len(r), hits.ctypes.data, mats.ctypes.data))
         return hits, mats
+
+
+class Refit:
+    """rp_refit: new vertex positions, vertex normals and sphere records for a DeviceScene, its tree refit in place
+    (include/rp.h).  Arrays as DeviceScene.geometry() numbers them; None means unchanged.  An update of the geometry names
+    all of it: positions when the scene has triangles, spheres when it has spheres.  The caller orders updates against
+    renders of the scene (streams); the scene's host description is not touched."""
+
+    def __init__(self, scene: DeviceScene, coord_max: float = 0.0):
+        h = ctypes.c_void_p()
+        F.check(F.rp().rp_refit_create(scene.handle, float(coord_max), ctypes.byref(h)))
+        self.scene = scene
+        self.handle = h
+
+    def info(self) -> dict:
+        """rp_refit_info: {"vertices", "spheres", "levels", "bound"}."""
+        nv, ns, nl, b = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_double()
+        F.check(F.rp().rp_refit_info(self.handle, ctypes.byref(nv), ctypes.byref(ns), ctypes.byref(nl), ctypes.byref(b)))
+        return {"vertices": nv.value, "spheres": ns.value, "levels": nl.value, "bound": b.value}
+
+    def update_device(self, positions=None, normals=None, spheres=None, status=None, stream=None):
+        """rp_scene_refit_device on `stream` (torch stream; default: current): torch f64 tensors on the scene's device,
+        positions and normals of 3 * vertices elements, spheres of 4 * spheres.  status: a torch int32 tensor of one
+        element (allocated when None).  Returns the status tensor: RP_REFIT_OUT_OF_BOUND or 0 once the stream got there."""
+        import torch
+        info = self.info()
+        dev = torch.device("cuda", self.scene.device)
+        for t, m in ((positions, 3 * info["vertices"]), (normals, 3 * info["vertices"]), (spheres, 4 * info["spheres"])):
+            if t is not None:
+                _check_tensor(t, torch.float64, m, dev)
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _check_tensor(status, torch.int32, 1, dev)
+        ptr = [t.data_ptr() if t is not None else None for t in (positions, normals, spheres)]
+        F.check(F.rp().rp_scene_refit_device(self.handle, ptr[0], ptr[1], ptr[2], status.data_ptr(), _stream_ptr(stream, dev)))
+        return status
+
+    def update(self, positions=None, normals=None, spheres=None) -> tuple:
+        """rp_scene_refit: the same from numpy arrays, synchronous.  -> (status, seconds of the kernels)."""
+        info = self.info()
+        arrs = []
+        for a, m in ((positions, 3 * info["vertices"]), (normals, 3 * info["vertices"]), (spheres, 4 * info["spheres"])):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+                if a.size != m:
+                    raise ValueError(f"a refit array of {a.size} doubles, the scene takes {m}")
+            arrs.append(a)
+        st, sec = ctypes.c_uint32(), ctypes.c_double()
+        F.check(F.rp().rp_scene_refit(self.handle, *[a.ctypes.data if a is not None else None for a in arrs],
+                                      ctypes.byref(st), ctypes.byref(sec)))
+        return st.value, sec.value
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            F.rp().rp_refit_destroy(self.handle)
+            self.handle = None
+            rs = self.scene.__dict__.get("_refits", [])
+            if self in rs:
+                rs.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def scene_geometry(scene: Scene) -> dict:
+    """DeviceScene.geometry() of a host scene."""
+    meshes = scene.scene_data.mesh_table
+    pos = np.concatenate([m.positions for m in meshes]) if meshes else np.zeros((0, 3))
+    nrm = np.concatenate([m.normals for m in meshes]) if meshes else np.zeros((0, 3))
+    root = np.asarray(scene.root, dtype=F.hittable_dtype())
+    sph = root[root["kind"] == F.RP_HITTABLE_SPHERE]
+    spheres = np.concatenate([sph["center"], sph["radius"][:, None]], axis=1) if len(sph) else np.zeros((0, 4))
+    return {"positions": np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3),
+            "normals": np.ascontiguousarray(nrm, dtype=np.float64).reshape(-1, 3),
+            "spheres": np.ascontiguousarray(spheres, dtype=np.float64).reshape(-1, 4)}
+
+
+def with_geometry(scene: Scene, positions=None, normals=None, spheres=None) -> Scene:
+    """A copy of a host scene with its geometry replaced (arrays as scene_geometry numbers them; None: kept): the
+    description a refit scene is compared with."""
+    from .scene import Mesh, SceneData
+    meshes, vb = [], 0
+    for m in scene.scene_data.mesh_table:
+        nv = len(m.positions)
+        meshes.append(Mesh(np.array(positions[vb:vb + nv]) if positions is not None else m.positions.copy(),
+                           np.array(normals[vb:vb + nv]) if normals is not None else m.normals.copy(),
+                           m.uvs, m.indices, m.material))
+        vb += nv
+    root = np.array(scene.root, dtype=F.hittable_dtype())
+    if spheres is not None:
+        rows = np.nonzero(root["kind"] == F.RP_HITTABLE_SPHERE)[0]
+        sp = np.asarray(spheres, dtype=np.float64).reshape(-1, 4)
+        root["center"][rows] = sp[:, :3]
+        root["radius"][rows] = sp[:, 3]
+    sd = SceneData(scene.scene_data.material_table, scene.scene_data.texture_table, meshes)
+    return Scene(scene.camera, sd, root, scene.background, scene.root_kind, scene.name)
+
+
+def refit_records_host(tree: dict, positions=None, normals=None, spheres=None, bound: float = 2.0 ** 54,
+                       tri_normals=None, n_vertices=None, n_spheres=None) -> int:
+    """rph_refit_records, the CPU model of Refit.update: refits `tree` (DeviceScene.tree()'s dict: "node_format", "root",
+    "nodes", "prims", "prim_refs") IN PLACE; tri_normals: the per-primitive normals (_ffi.tri_normals_dtype, rewritten
+    when normals are given).  bound: finite.  n_vertices, n_spheres default to the arrays' lengths.  -> the status."""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (positions, normals, spheres)]
+    nv = n_vertices if n_vertices is not None else max([a.size // 3 for a in arrs[:2] if a is not None], default=0)
+    ns = n_spheres if n_spheres is not None else (arrs[2].size // 4 if arrs[2] is not None else 0)
+    ptr = [a.ctypes.data if a is not None and a.size else None for a in arrs]
+    for k in ("nodes", "prims", "prim_refs"):
+        assert tree[k].flags["C_CONTIGUOUS"]
+    st = ctypes.c_uint32()
+    F.check_host(F.host().rph_refit_records(tree["node_format"], tree["nodes"].ctypes.data, len(tree["nodes"]), tree["root"],
+                                            tree["prims"].ctypes.data, tree["prim_refs"].ctypes.data,
+                                            tri_normals.ctypes.data if tri_normals is not None else None,
+                                            len(tree["prims"]), ptr[0], ptr[1], ptr[2], nv, ns, bound, ctypes.byref(st)))
+    return st.value
 
 
 class Workspace:
